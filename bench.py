@@ -1,6 +1,7 @@
 """Benchmark of the MI355X HiFi-GAN Generator hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--preset v1] [--batch 8] [--frames 1024]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +16,13 @@ sharded over ranks (weak scaling); weights are generated on rank 0 and
 broadcast once with RCCL.  Rank 0 prints ONE JSON line.
 
 Timing: `value` is K uninstrumented steps of the production schedule (batch halves on
-two HIP streams).  Roofline: a second timed pass of the same K steps on one stream with
+two HIP streams); `ms_per_step` is the wall time of one of them.  A plain run does only
+that: set up, W warm-up steps, the K timed steps, the line.  `--dump-outputs DIR` also
+writes the wav the last timed step computed to DIR/wav.npy (float32; mel and weights are
+seeded, so two builds can be compared sample for sample).
+
+Everything below is measured only with `--full` (each part still has its --no-* switch).
+Roofline: a second timed pass of the same K steps on one stream with
 every kernel launch bracketed by HIP events on that stream (libhifigan_hip profiling
 mode); the dominant kernel's achieved TFLOP/s = its algorithmic FLOP ÷ its summed
 launch time (with two streams the halves' intervals overlap, so they cannot be
@@ -124,8 +131,21 @@ def parse():
                          "bars, tests/test_gpu_stages.py), bf16x3 (bf16 halves: faster, ~16-bit "
                          "products), exact fp32 MFMA, or bf16w (weights stored as bf16: a "
                          "different model, parity against the bf16-rounded weights)")
-    ap.add_argument("--also", nargs="*", default=["bf16x3", "fp32", "bf16w"],
-                    help="extra precisions measured in the same run (reported under 'alt')")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline pass, measure everything else this benchmark "
+                         "reports: the other precisions (--also), the 1-stream per-kernel "
+                         "roofline pass and the live MFMA probe, the rocprofv3 PMC traffic "
+                         "passes, the end-to-end figure, the wav checksum, the other BASELINE "
+                         "configs and the CPU baseline (each still switched off by its --no-* "
+                         "option).  Off by default: a plain run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the wav of the last timed step (this "
+                         "rank's [batch, 1, samples], float32) to DIR/wav.npy; above 64 MB a "
+                         "fixed seeded sample of its elements")
+    ap.add_argument("--also", nargs="*", default=None,
+                    help="with --full: extra precisions measured in the same run (reported "
+                         "under 'alt'; default bf16x3 fp32 bf16w)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--force-dist", action="store_true",
@@ -151,7 +171,34 @@ def parse():
                     help="schedule overrides for A/B runs (hfg_debug_schedule_set, e.g. "
                          "RB_PERSIST=0); recorded in the line's config")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.full:
+        if args.also is None:
+            args.also = ["bf16x3", "fp32", "bf16w"]
+    else:
+        if args.also:
+            ap.error("--also PRECISION ... needs --full")
+        # a plain run: the headline pass only
+        args.also = []
+        args.no_profile = args.no_pmc = args.no_extra = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, wav):
+    """Write the timed path's last output (a host float32 array) as DIR/wav.npy; an array
+    above DUMP_LIMIT_BYTES is cut to a fixed seeded sample of its elements (the distinct
+    flat indices numpy's default_rng(0) draws, ascending: the same for every run of the
+    same shape)."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(wav, dtype=np.float32)
+    keep = DUMP_LIMIT_BYTES // 4 - 1024  # room for the .npy header
+    if a.size > keep:
+        idx = np.unique(np.random.default_rng(0).integers(0, a.size, size=keep))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(dirname, "wav.npy"), a)
 
 
 # FETCH_SIZE / WRITE_SIZE corrections measured by profiles/pmc_calib.hip on gfx950
@@ -621,6 +668,9 @@ def main():
         step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
         ev_median[precision] = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else \
             0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+        if args.dump_outputs and rank == 0 and precision == args.precision:
+            # what the last timed step left in wav, before any later pass writes it again
+            last_wav.append(wav.cpu().numpy())
         if use_dist:
             dist.barrier()
             t = torch.zeros(world, dtype=torch.float64, device=coll_dev)
@@ -655,8 +705,9 @@ def main():
                 h.set_streams(args.streams)
         # content hash of the value pass's output (hfg_checksum32): same-box A/B builds that must
         # be bitwise equal show it (profiles/r06/lib_ab.sh)
-        wav_sum[precision] = int(pkg._lib.checksum32([wav])[0]) & 0xffffffff
-        if precision == args.precision and not args.pmc_child:
+        if args.full:
+            wav_sum[precision] = int(pkg._lib.checksum32([wav])[0]) & 0xffffffff
+        if args.full and precision == args.precision and not args.pmc_child:
             e2e[precision] = end_to_end(eager_step, wav)
         del ws, wav
         return elapsed, prof, out_len
@@ -689,6 +740,7 @@ def main():
     ev_median = {}  # per-step HIP-event median (ms) of the value pass, per precision
     wav_sum = {}  # hfg_checksum32 of the value pass's wav, per precision
     e2e = {}
+    last_wav = []  # --dump-outputs: rank 0's wav of the last timed step (headline precision)
     def progress(msg):
         """one stderr line per phase (a long run then shows it is alive)"""
         if rank == 0:
@@ -696,6 +748,8 @@ def main():
 
     progress(f"measuring {args.precision}")
     elapsed, prof, out_len = measure(args.precision)
+    if last_wav:
+        dump_outputs(args.dump_outputs, last_wav.pop())
     alt = {}
     for prec in args.also:
         if prec != args.precision:
@@ -718,6 +772,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "weak",
