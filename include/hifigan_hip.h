@@ -96,7 +96,17 @@ extern "C" {
 
 typedef struct hfg_handle hfg_handle;
 
-/* Hyper-parameters: models/hifigan.py:149-158 constructor arguments. */
+/* Hyper-parameters: models/hifigan.py:149-158 constructor arguments, then the two places
+ * where the public HiFi-GAN release's Generator (jik876/hifi-gan models.py) differs from
+ * the reference's.  A zero-initialised tail is the reference's Generator.
+ *   resblock_type 1: the release's ResBlock2 (config "resblock": "2", generator V3): one
+ *                    conv per dilation, x = x + conv_m(lrelu(x, 0.1)); parameters
+ *                    "mrfs.{i}.resblocks.{j}.convs.{m}.{weight,bias}" (or weight_g /
+ *                    weight_v) in place of convs1 / convs2.
+ *   post_slope     : slope of the leaky_relu in front of conv_post.  The release runs
+ *                    F.leaky_relu(x) there, PyTorch's default 0.01, in every generator
+ *                    (V1, V2, V3); the reference 0.1 (models/hifigan.py:254).  Finite,
+ *                    in [0, 1). */
 typedef struct hfg_config {
     int32_t n_mels;                              /* 80                        */
     int32_t n_up;                                /* len(upsample_rates)       */
@@ -108,6 +118,8 @@ typedef struct hfg_config {
     int32_t n_dil[HFG_MAX_RES];                  /* len(dilations[j])         */
     int32_t dil[HFG_MAX_RES][HFG_MAX_DIL];       /* [[1,3,5],[1,3,5],[1,3,5]] */
     int32_t dtype;                               /* HFG_DTYPE_*               */
+    int32_t resblock_type;                       /* 0: reference ResBlock (conv pairs), 1: ResBlock2 */
+    float post_slope;                            /* 0.0f: the reference's 0.1 */
 } hfg_config;
 
 /* Library version string, e.g. "hifigan_hip 0.1.0 gfx950". */
@@ -193,6 +205,8 @@ typedef struct hfg_mrf_config {
     int32_t n_dil[HFG_MAX_RES];
     int32_t dil[HFG_MAX_RES][HFG_MAX_DIL];
     int32_t dtype;                               /* HFG_DTYPE_*               */
+    int32_t resblock_type;                       /* as in hfg_config: 1 = ResBlock2, keys
+                                                    "resblocks.{j}.convs.{m}.*" */
 } hfg_mrf_config;
 
 int hfg_mrf_create(const hfg_mrf_config* cfg, int device, hfg_handle** out);

@@ -59,6 +59,8 @@ class HfgConfig(ctypes.Structure):
         ("n_dil", c_int32 * HFG_MAX_RES),
         ("dil", (c_int32 * HFG_MAX_DIL) * HFG_MAX_RES),
         ("dtype", c_int32),
+        ("resblock_type", c_int32),
+        ("post_slope", c_float),
     ]
 
 
@@ -73,12 +75,24 @@ class HfgMrfConfig(ctypes.Structure):
         ("n_dil", c_int32 * HFG_MAX_RES),
         ("dil", (c_int32 * HFG_MAX_DIL) * HFG_MAX_RES),
         ("dtype", c_int32),
+        ("resblock_type", c_int32),
     ]
 
 
+# the release's config.json "resblock" value -> hfg_config.resblock_type
+RESBLOCK_TYPES = {"1": 0, "2": 1}
+
+
+def _resblock_type(resblock) -> int:
+    if str(resblock) not in RESBLOCK_TYPES:
+        raise ValueError(f"resblock must be '1' or '2', got {resblock!r}")
+    return RESBLOCK_TYPES[str(resblock)]
+
+
 def make_mrf_config(channels, resblock_kernel_sizes, resblock_dilation_sizes,
-                    precision: str = "fp32") -> HfgMrfConfig:
-    """One MRF's hyper-parameters (MRF.__init__, models/hifigan.py:96-114)."""
+                    precision: str = "fp32", *, resblock: str = "1") -> HfgMrfConfig:
+    """One MRF's hyper-parameters (MRF.__init__, models/hifigan.py:96-114); resblock "2":
+    the public release's ResBlock2 (one conv per dilation)."""
     n = min(len(resblock_kernel_sizes), len(resblock_dilation_sizes))  # zip semantics
     if n > HFG_MAX_RES:
         raise ValueError("too many resblocks for the ABI")
@@ -96,11 +110,16 @@ def make_mrf_config(channels, resblock_kernel_sizes, resblock_dilation_sizes,
     if precision not in DTYPES:
         raise ValueError(f"precision must be one of {sorted(DTYPES)}")
     c.dtype = DTYPES[precision]
+    c.resblock_type = _resblock_type(resblock)
     return c
 
 
 def make_config(n_mels, upsample_rates, upsample_kernel_sizes, upsample_initial_channel,
-                resblock_kernel_sizes, resblock_dilation_sizes, precision: str = "fp32") -> HfgConfig:
+                resblock_kernel_sizes, resblock_dilation_sizes, precision: str = "fp32", *,
+                resblock: str = "1", final_lrelu_slope: float = 0.1) -> HfgConfig:
+    """The Generator's hyper-parameters.  resblock "2" and final_lrelu_slope 0.01 give the
+    public HiFi-GAN release's Generator (include/hifigan_hip.h, hfg_config); the defaults
+    leave the struct's tail zero: the reference's."""
     if len(upsample_rates) != len(upsample_kernel_sizes):
         raise ValueError("upsample_rates and upsample_kernel_sizes differ in length")
     if len(resblock_kernel_sizes) != len(resblock_dilation_sizes):
@@ -128,6 +147,11 @@ def make_config(n_mels, upsample_rates, upsample_kernel_sizes, upsample_initial_
     if precision not in DTYPES:
         raise ValueError(f"precision must be one of {sorted(DTYPES)}")
     c.dtype = DTYPES[precision]
+    c.resblock_type = _resblock_type(resblock)
+    # 0.0f in the struct means the reference's 0.1, so a zero slope itself is not expressible
+    if not 0.0 < float(final_lrelu_slope) < 1.0:
+        raise ValueError(f"final_lrelu_slope must be in (0, 1), got {final_lrelu_slope!r}")
+    c.post_slope = 0.0 if float(final_lrelu_slope) == 0.1 else float(final_lrelu_slope)
     return c
 
 

@@ -14,7 +14,15 @@ layouts a HiFi-GAN vocoder checkpoint comes in onto this package's
   ``{"generator": sd}``, weight-normed ``conv_pre`` / ``conv_post``, ResBlocks indexed
   flat as ``resblocks.{stage * num_kernels + j}``) — remapped to
   ``mrfs.{stage}.resblocks.{j}`` and its ``conv_pre`` / ``conv_post`` weight norm
-  folded (the reference applies none there);
+  folded (the reference applies none there).  The keys are only half of it: the
+  release's Generator is not the reference's.  It runs ``F.leaky_relu(x)`` — slope
+  0.01, not 0.1 — in front of ``conv_post`` in every generator (V1, V2, V3), and its
+  V3 (``"resblock": "2"``) is built from ResBlock2 blocks (``convs.{m}``, one conv per
+  dilation).  Exact release parity therefore needs a Generator built by
+  ``generator_from_release_config(config_json_dict)`` (``resblock=h["resblock"]``,
+  ``final_lrelu_slope=0.01``); loaded into a default ``HiFiGANGenerator()`` a release
+  V1 / V2 file computes the reference's forward on the release's weights (off by up
+  to ~1e-3..1e-1 in the wav), and a V3 file does not load at all;
 * container dicts ``{"generator" | "state_dict" | "model" | "model_state_dict": sd}``
   and DistributedDataParallel ``module.`` prefixes.
 
@@ -95,6 +103,24 @@ def convert_state_dict(obj, num_kernels: int, num_upsamples: int,
     if not weight_normed:
         out = fold_weight_norm(out)
     return out
+
+
+def generator_from_release_config(h: Mapping, precision: Optional[str] = None):
+    """The Generator of the public HiFi-GAN release for its ``config.json`` (as a mapping):
+    keys ``resblock`` ("1" or "2"), ``upsample_rates``, ``upsample_kernel_sizes``,
+    ``upsample_initial_channel``, ``resblock_kernel_sizes``, ``resblock_dilation_sizes`` and
+    optionally ``num_mels`` (80).  It differs from ``HiFiGANGenerator(**the same lists)`` by
+    ``resblock=h["resblock"]`` and the release's final ``F.leaky_relu(x)`` slope 0.01; load
+    the release's ``generator_*`` file into it with ``load_generator_checkpoint``."""
+    from .hifigan import HiFiGANGenerator
+    return HiFiGANGenerator(
+        n_mels=int(h.get("num_mels", 80)),
+        upsample_rates=list(h["upsample_rates"]),
+        upsample_kernel_sizes=list(h["upsample_kernel_sizes"]),
+        upsample_initial_channel=int(h["upsample_initial_channel"]),
+        resblock_kernel_sizes=list(h["resblock_kernel_sizes"]),
+        resblock_dilation_sizes=[list(d) for d in h["resblock_dilation_sizes"]],
+        precision=precision, resblock=str(h["resblock"]), final_lrelu_slope=0.01)
 
 
 def load_generator_checkpoint(gen, src: Union[str, Mapping], strict: bool = True,

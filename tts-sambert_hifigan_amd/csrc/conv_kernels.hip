@@ -42,6 +42,8 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(1))) void* gptr_t;
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * kLReluSlope; }
+// conv_post's input activation: the slope is the handle's (0.1 reference, 0.01 release)
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 template <int KT_, int WM, int WN, int WAVES_M, int WAVES_N, int CK, bool UPS>
 __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, 3)
@@ -249,7 +251,7 @@ conv1d_mfma_f32(const ConvParams p) {
 __global__ void __launch_bounds__(256)
 conv_post_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const float* __restrict__ w,
                const float* __restrict__ bias, float* __restrict__ wav,
-               const int32_t* __restrict__ lens) {
+               const int32_t* __restrict__ lens, float slope) {
   constexpr int TT = 256, KP = 7, HALO = 3;
   constexpr int XW = TT + KP - 1;
   constexpr int CBLK = kConvPostCB;
@@ -290,8 +292,8 @@ conv_post_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const fl
 #pragma unroll
       for (int e = 0; e < CB; ++e) {
         if (c0 + e >= nc) break;
-        Xs[(c0 + e) * XW + tt] = okm ? lrelu(vm[e]) : 0.f;
-        if (tt < KP - 1) Xs[(c0 + e) * XW + TT + tt] = okh ? lrelu(vh[e]) : 0.f;
+        Xs[(c0 + e) * XW + tt] = okm ? lrelu(vm[e], slope) : 0.f;
+        if (tt < KP - 1) Xs[(c0 + e) * XW + TT + tt] = okh ? lrelu(vh[e], slope) : 0.f;
       }
     }
     __syncthreads();
@@ -315,7 +317,7 @@ conv_post_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const fl
 __global__ void __launch_bounds__(256)
 conv_post4_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const float* __restrict__ w,
                 const float* __restrict__ bias, float* __restrict__ wav,
-                const int32_t* __restrict__ lens) {
+                const int32_t* __restrict__ lens, float slope) {
   constexpr int KP = 7, CB = 8;
   typedef float f4 __attribute__((ext_vector_type(4)));
   const int b = blockIdx.y;
@@ -362,7 +364,7 @@ conv_post4_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const f
 #pragma unroll
       for (int k = 0; k < 12; ++k) {
         const float r = q[e][k >> 2][k & 3];
-        v[k] = okv[k] ? lrelu(r) : 0.f;
+        v[k] = okv[k] ? lrelu(r, slope) : 0.f;
       }
       const float* ws = w + (c0 + e) * KP;
 #pragma unroll
@@ -451,12 +453,12 @@ hipError_t launch_conv(TileId tile, int kt, bool ups, const ConvParams& p, int n
 }
 
 hipError_t launch_conv_post(const float* x, int64_t x_bs, int C, int L, const float* w,
-                            const float* bias, float* wav, const int32_t* lens, int batch,
-                            hipStream_t stream, const char** name, bool quad) {
+                            const float* bias, float* wav, const int32_t* lens, float slope,
+                            int batch, hipStream_t stream, const char** name, bool quad) {
   if (quad && conv_post4_ok(L) && (int64_t)C * L <= ((int64_t)1 << 30)) {
     if (name) *name = "conv_post4_tanh";
     dim3 grid((L / 4 + 255) / 256, batch);
-    conv_post4_tanh<<<grid, dim3(256), 0, stream>>>(x, x_bs, C, L, w, bias, wav, lens);
+    conv_post4_tanh<<<grid, dim3(256), 0, stream>>>(x, x_bs, C, L, w, bias, wav, lens, slope);
     return hipGetLastError();
   }
   const size_t lds = conv_post_lds_bytes(C);
@@ -465,7 +467,7 @@ hipError_t launch_conv_post(const float* x, int64_t x_bs, int C, int L, const fl
     return err;
   if (name) *name = "conv_post_tanh";
   dim3 grid((L + 255) / 256, batch);
-  conv_post_tanh<<<grid, dim3(256), lds, stream>>>(x, x_bs, C, L, w, bias, wav, lens);
+  conv_post_tanh<<<grid, dim3(256), lds, stream>>>(x, x_bs, C, L, w, bias, wav, lens, slope);
   return hipGetLastError();
 }
 

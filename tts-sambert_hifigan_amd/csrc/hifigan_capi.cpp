@@ -275,6 +275,13 @@ int validate_config(const hfg_config* c) {
     return fail(HFG_EINVAL, "dtype must be HFG_DTYPE_FP32 (0), HFG_DTYPE_BF16X3 (1), "
                 "HFG_DTYPE_BF16W (2) or HFG_DTYPE_F16X3 (3)");
   if (c->c0 <= 0) return fail(HFG_EINVAL, "upsample_initial_channel must be > 0");
+  if (c->resblock_type != 0 && c->resblock_type != 1)
+    return fail(HFG_EINVAL, "resblock_type must be 0 (the reference's ResBlock) or 1 (ResBlock2), "
+                "got %d", c->resblock_type);
+  // the kernels' leaky_relu is max(v, s v): s < 1
+  if (!std::isfinite(c->post_slope) || c->post_slope < 0.f || c->post_slope >= 1.f)
+    return fail(HFG_EINVAL, "post_slope must be finite and in [0, 1) (0 = the reference's 0.1), "
+                "got %g", (double)c->post_slope);
   for (int i = 0; i < c->n_up; ++i) {
     if (c->up_rates[i] <= 0 || c->up_kernels[i] <= 0)
       return fail(HFG_EINVAL, "upsample rate/kernel %d must be > 0", i);
@@ -335,6 +342,13 @@ Stage build_stage(hfg_handle* h, int ch, const std::string& pre) {
   for (int j = 0; j < c.n_res; ++j) {
     const int kr = c.res_kernels[j];
     const std::string rb = pre + "resblocks." + std::to_string(j);
+    if (c.resblock_type == 1) {
+      // ResBlock2: one conv per dilation, "<pre>resblocks.{j}.convs.{m}" (kept in conv1)
+      for (int m = 0; m < c.n_dil[j]; ++m)
+        st.conv1.push_back(add_conv(h, L_CONV, rb + ".convs." + std::to_string(m), ch, ch, kr,
+                                    c.dil[j][m], get_padding(kr, c.dil[j][m])));
+      continue;
+    }
     for (int m = 0; m < c.n_dil[j]; ++m)
       st.conv1.push_back(add_conv(h, L_CONV, rb + ".convs1." + std::to_string(m), ch, ch, kr,
                                   c.dil[j][m], get_padding(kr, c.dil[j][m])));
@@ -487,6 +501,31 @@ int build_layers(hfg_handle* h) {
       const int nwin = C == 128 ? 256 : C == 64 ? (rb.kt == 3 ? 256 : 512) : 512;
       rb.nwin = nwin;
       rb.wm = 1;
+      if (c.resblock_type == 1) {
+        // ResBlock2 (resblock2_bf16x3): n_dil convs; the first is exact on the whole window
+        // (margin rows), so the halo is the radius of the convs after it.  One launch per
+        // block, one window per thread block (no split, no persistent grid, no fused conv_post)
+        bool ok2 = rb.kt % 2 == 1 && hfg::rb2_supported(C, rb.kt, nwin, rb.wm) &&
+                   c.n_dil[j] <= hfg::kRbMaxConv;
+        for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
+          rb.convs.push_back(st.conv1[idx]);
+          if (m > 0) rb.halo += (rb.kt - 1) / 2 * c.dil[j][m];
+          if ((rb.kt - 1) / 2 * c.dil[j][m] > hfg::rb_marg(C, nwin)) ok2 = false;
+        }
+        rb.W = (nwin - 2 * rb.halo) & ~3;
+        if (rb.W < nwin / 4) ok2 = false;
+        if (C == 128 && (double)nwin / rb.W > 1.15) ok2 = false;
+        if (!ok2) continue;
+        rb.fused = true;
+        rb.w_off = off;
+        rb.w_len = (size_t)rb.convs.size() * C * C * rb.kt;
+        off += (rb.w_len + 63) & ~(size_t)63;
+        rb.b_off = off;
+        rb.b_len = rb.convs.size() * (size_t)C;
+        off += (rb.b_len + 63) & ~(size_t)63;
+        st.rbs[j] = std::move(rb);
+        continue;
+      }
       bool ok = rb.kt % 2 == 1 && hfg::rb_supported(C, rb.kt, nwin, rb.wm) &&
                 2 * c.n_dil[j] <= hfg::kRbMaxConv;
       for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
@@ -555,7 +594,8 @@ int build_layers(hfg_handle* h) {
   for (auto& st : h->stages) {
     const int C = st.C;
     const int nwin = hfg::thin_window(C);
-    if (nwin == 0 || c.n_res > hfg::kThinMaxRes) continue;
+    // (the mrf_thin kernels compute dilation pairs only: ResBlock2 stages run layer by layer)
+    if (nwin == 0 || c.n_res > hfg::kThinMaxRes || c.resblock_type == 1) continue;
     int n_conv = 0, halo_max = 0;
     bool ok = true;
     std::vector<int> convs, conv0, halos;
@@ -1172,10 +1212,17 @@ int run_conv(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_
   return HFG_OK;
 }
 
+// slope of the leaky_relu in front of conv_post: the reference's 0.1 (models/hifigan.py:254)
+// unless the config names another (the public release's F.leaky_relu(x) default, 0.01)
+inline float post_slope_of(const hfg_handle* h) {
+  return h->cfg.post_slope ? h->cfg.post_slope : hfg::kLReluSlope;
+}
+
 struct PostFuse {
   const float* w;  // conv_post weight [C][7], bias [1] (packed fp32)
   const float* b;
   float* wav;      // [B][L]
+  float slope;     // of the leaky_relu in front of conv_post (post_slope_of)
 };
 
 // One whole ResBlock (all dilations) + its MRF contribution in one launch.
@@ -1226,7 +1273,8 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     // window's MRF round trip; launch_resblock_bf16x3 runs it where a persistent variant is
     // built, C = 64 with the 512-column window).  HFG_RB_PERSIST: 0 off, 1 one block per CU
     // of the half-batch stream's share (n_CU / halves), 2 one per CU
-    if (h->rb_persist && per_cu == 1 && !(last && post))
+    const bool rb2 = h->cfg.resblock_type == 1;  // resblock2_bf16x3: one window per block
+    if (h->rb_persist && per_cu == 1 && !(last && post) && !rb2)
       p.persist = std::max(1, h->n_cu / (h->rb_persist == 1 ? h->halves : 1));
     double bytes =
         4.0 * B * Lt * C * ((last && (mrf_mode & 1)) ? 3 : 2) + 4.0 * (double)rb.w_len;
@@ -1236,6 +1284,7 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
       p.W = (rb.nwin - 2 * p.halo) & ~3;
       p.post_w = post->w;
       p.post_b = post->b;
+      p.post_slope = post->slope;
       p.wav = post->wav;
       p.amax_out = nullptr;  // no consumer of the stage output's scale
       bytes -= 4.0 * B * Lt * (C - 1);
@@ -1243,8 +1292,10 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     const char* name = nullptr;
     ln.begin(flop, bytes);
     hipError_t e =
-        hfg::launch_resblock_bf16x3(C, rb.nwin, rb.wm, rb.kt, h->fmt, h->np, p, (int)B, ln.stream,
-                                    &name);
+        rb2 ? hfg::launch_resblock2_bf16x3(C, rb.nwin, rb.wm, rb.kt, h->fmt, h->np, p, (int)B,
+                                           ln.stream, &name)
+            : hfg::launch_resblock_bf16x3(C, rb.nwin, rb.wm, rb.kt, h->fmt, h->np, p, (int)B,
+                                          ln.stream, &name);
     ln.end(name);
     if (e != hipSuccess)
       return fail(HFG_EIO, "launch resblock %s: %s", L0.mod.c_str(), hipGetErrorString(e));
@@ -1410,6 +1461,26 @@ int run_one_rb(hfg_handle* h, Launcher& ln, const Stage& st, int j, int idx, con
                         post);
   int rc;
   const uint32_t* asrc = ax;
+  if (c.resblock_type == 1) {
+    // ResBlock2, one launch per dilation: x = x + conv_m(lrelu(x)).  The conv reads a
+    // neighbourhood of x, so it writes the other of R / Tb; the last one carries the MRF epilogue
+    const float* src = X;
+    for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
+      const Layer& Lm = h->layers[st.conv1[idx]];
+      if (m < c.n_dil[j] - 1) {
+        float* dst = (m & 1) ? Tb : R;
+        uint32_t* ar = ln.take();
+        rc = run_conv(h, ln, Lm, src, B, L, dst, true, false, src, nullptr, 0, 1.f, lens, asrc, ar);
+        src = dst;
+        asrc = ar;
+      } else {
+        rc = run_conv(h, ln, Lm, src, B, L, nullptr, true, false, src, out, mode, (float)c.n_res,
+                      lens, asrc, aout);
+      }
+      if (rc) return rc;
+    }
+    return HFG_OK;
+  }
   for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
     const float* src = (m == 0) ? X : R;
     const Layer& L1 = h->layers[st.conv1[idx]];
@@ -1535,7 +1606,7 @@ bool post_fusable(const hfg_handle* h, const Stage& st, int64_t L, bool conc_st,
                   float* const* taps) {
   const hfg_config& c = h->cfg;
   if (!h->fuse_post || h->conv_post < 0 || taps || conc_st || st.thin || st.C != 32 ||
-      L % 4 != 0 || h->layers[h->conv_post].C_in != 32)
+      L % 4 != 0 || h->layers[h->conv_post].C_in != 32 || c.resblock_type == 1)
     return false;
   const RbFused& rb = st.rbs[c.n_res - 1];
   if (!rb.fused || rb.nwin != 512 || rb.wm != 1) return false;
@@ -1656,7 +1727,8 @@ int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hf
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(wav)");
       }
       const Layer& Lp = h->layers[h->conv_post];
-      const PostFuse pf{h->packed_dev + Lp.w_off, h->packed_dev + Lp.b_off, wav};
+      const PostFuse pf{h->packed_dev + Lp.w_off, h->packed_dev + Lp.b_off, wav,
+                        post_slope_of(h)};
       rc = run_mrf(h, ln, st, X, B, L, R, Tb, MRF, lens_at(i + 1), -1, a_x, a_cur, nullptr, &pf);
       if (rc) return rc;
       if (sl.overflow) return fail(HFG_EIO, "internal: f16x3 scale slots exhausted");
@@ -1677,7 +1749,7 @@ int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hf
     ln.begin(2.0 * Lp.C_in * 7 * (double)L * B, 4.0 * B * L * (Lp.C_in + 1));
     hipError_t e = hfg::launch_conv_post(cur, (int64_t)Lp.C_in * L, Lp.C_in, (int)L,
                                          h->packed_dev + Lp.w_off, h->packed_dev + Lp.b_off, wav,
-                                         lens_at(c.n_up), (int)B, stream, &name);
+                                         lens_at(c.n_up), post_slope_of(h), (int)B, stream, &name);
     ln.end(name);
     if (e != hipSuccess) return fail(HFG_EIO, "launch conv_post: %s", hipGetErrorString(e));
   }
@@ -1872,6 +1944,7 @@ int hfg_mrf_create(const hfg_mrf_config* mc, int device, hfg_handle** out) {
     for (int m = 0; m < HFG_MAX_DIL; ++m) c.dil[j][m] = mc->dil[j][m];
   }
   c.dtype = mc->dtype;
+  c.resblock_type = mc->resblock_type;
   return create_impl(&c, true, device, out);
 }
 
@@ -1926,6 +1999,16 @@ int hfg_set_weight(hfg_handle* h, const char* name, const void* data, const int6
     size_t l = strlen(suf);
     return key.size() > l && key.compare(key.size() - l, l, suf) == 0;
   };
+  // a ResBlock key of the other block type: say which layout this handle holds
+  const bool pair_key = key.find(".convs1.") != std::string::npos ||
+                        key.find(".convs2.") != std::string::npos;
+  if (h->cfg.resblock_type == 1 && pair_key)
+    return fail(HFG_EINVAL, "key '%s': this handle holds ResBlock2 blocks (resblock_type 1), whose "
+                "parameters are resblocks.{j}.convs.{m}.*, not convs1 / convs2", name);
+  if (h->cfg.resblock_type == 0 && key.find(".convs.") != std::string::npos)
+    return fail(HFG_EINVAL, "key '%s': this handle holds the reference's ResBlock (resblock_type "
+                "0), whose parameters are resblocks.{j}.convs1.{m}.* / convs2.{m}.*; create it "
+                "with resblock_type 1 for ResBlock2's convs.{m}", name);
   if (ends_with(".weight_g") || ends_with(".weight_v")) {
     // apply_weight_norm layout (models/hifigan.py:274-283): w = g * v / ||v||, dim=0
     const std::string mod = key.substr(0, key.size() - 9);

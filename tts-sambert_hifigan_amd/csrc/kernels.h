@@ -277,6 +277,7 @@ struct RbParams {
   int persist;
   int dbg;               // ablations (HFG_DEBUG_FLAGS, wrong results when set): bit4 no MRF
                          // epilogue, bit5 no x loads, bit6 no operand writes
+  float post_slope;      // fused conv_post: slope of the leaky_relu in front of it
 };
 // divisors whose fma-refined reciprocal quotient equals the IEEE quotient for every fp32
 // input (div_exact, bf16x3_common.h; verified exhaustively, tests/tools/verify_fast_div.c)
@@ -288,6 +289,13 @@ size_t rb_lds_bytes(int C, int nwin, int n_conv);
 hipError_t launch_resblock_bf16x3(int C, int nwin, int wm, int kt, int fmt, int np,
                                   const RbParams& p, int batch, hipStream_t stream,
                                   const char** name);
+// The public HiFi-GAN release's ResBlock2 (one conv per dilation, x = x + conv_m(lrelu(x)))
+// on the same windows, operand planes and A-stream order: p.n_conv = n_dil convs (any
+// count from 1), one window per block (p.persist, p.conv0 and p.wav must be 0 / null).
+bool rb2_supported(int C, int kt, int nwin, int wm);
+hipError_t launch_resblock2_bf16x3(int C, int nwin, int wm, int kt, int fmt, int np,
+                                   const RbParams& p, int batch, hipStream_t stream,
+                                   const char** name);
 
 // ---- whole MRF per launch for thin stages, C <= 16 (mrf_thin.hip) ----
 // All ResBlocks of one MRF on a time window in LDS, packed-fp32 VALU dot products (exact
@@ -344,13 +352,14 @@ constexpr int kConvPostCB = 32;
 inline size_t conv_post_lds_bytes(int C) {
   return sizeof(float) * ((size_t)((C * 7 + 3) & ~3) + (size_t)(C < kConvPostCB ? C : kConvPostCB) * (256 + 6));
 }
-// conv_post + tanh: wav[b][t] = tanh(bias + sum_{c,j} w[c][j] * lrelu(x[b][c][t+j-3]))
-// for t < lens[b] (lens null = L); 0 beyond.  quad: the 4-samples-per-thread kernel
+// conv_post + tanh: wav[b][t] = tanh(bias + sum_{c,j} w[c][j] * lrelu(x[b][c][t+j-3], slope))
+// for t < lens[b] (lens null = L); 0 beyond.  slope: kLReluSlope for the reference, 0.01 for
+// the public release's Generator.  quad: the 4-samples-per-thread kernel
 // (conv_post4_tanh) where L % 4 == 0 — bitwise the LDS-staged one.
 inline bool conv_post4_ok(int L) { return L % 4 == 0; }
 hipError_t launch_conv_post(const float* x, int64_t x_bs, int C, int L, const float* w,
-                            const float* bias, float* wav, const int32_t* lens, int batch,
-                            hipStream_t stream, const char** name, bool quad = true);
+                            const float* bias, float* wav, const int32_t* lens, float slope,
+                            int batch, hipStream_t stream, const char** name, bool quad = true);
 
 // Content hash of up to kChecksumMax fp32 tensors per launch: out[base + i] +=
 // sum_w mix(word_w, w) over tensor i's n[i] 32-bit words (out zeroed by the caller).

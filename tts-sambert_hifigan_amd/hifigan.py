@@ -5,6 +5,8 @@ Mirrors ``models/hifigan.py`` of terrense/TTS-sambert_hifiGAN:
 
 * ``get_padding``          models/hifigan.py:21-23
 * ``ResBlock``             models/hifigan.py:26-86   (parameter container)
+* ``ResBlock2``            no reference counterpart: the public HiFi-GAN release's
+                           one-conv-per-dilation block (its generator V3)
 * ``MRF``                  models/hifigan.py:89-131  (parameter container)
 * ``HiFiGANGenerator``     models/hifigan.py:134-283 (same ctor signature, same
                            submodule tree ⇒ identical state_dict keys, same
@@ -237,23 +239,68 @@ class ResBlock(_HipWeights):
         return self._run_block(x, self.channels, 0)
 
 
+class ResBlock2(_HipWeights):
+    """The public HiFi-GAN release's ResBlock2 (jik876/hifi-gan models.py, config
+    ``"resblock": "2"``, generator V3): ``convs[m]`` = Conv1d(C, C, k, dilation=d_m);
+    forward = for each m: x = x + conv_m(lrelu(x, 0.1)).  The reference has no such class.
+    Inside a Generator its computation is part of the fused schedule; called on its own
+    it runs ``hfg_resblock_forward`` on an MRF handle of this one block."""
+
+    def __init__(self, channels: int, kernel_size: int = 3, dilation: Tuple[int, ...] = (1, 3),
+                 *, precision: Optional[str] = None):
+        super().__init__()
+        self.channels = channels
+        self.kernel_size = kernel_size
+        self.dilation = tuple(dilation)
+        self.convs = nn.ModuleList()
+        for d in dilation:
+            self.convs.append(nn.Conv1d(channels, channels, kernel_size, stride=1, dilation=d,
+                                        padding=get_padding(kernel_size, d)))
+        self._hip_setup(precision)
+
+    def _hip_weight_slots(self):
+        return self._conv_slots(self, "resblocks.0.")
+
+    def _hip_new_handle(self, idx):
+        cfg = _lib.make_mrf_config(self.channels, [self.kernel_size], [list(self.dilation)],
+                                   precision=self.precision, resblock="2")
+        return _lib.Handle(cfg, idx, mrf=True)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, C, T] -> [B, C, T]."""
+        if not self.dilation:
+            return x
+        return self._run_block(x, self.channels, 0)
+
+
+def _block_convs(resblock: nn.Module):
+    """Every conv of a ResBlock (convs1 then convs2) or ResBlock2 (convs)."""
+    if isinstance(resblock, ResBlock2):
+        return list(resblock.convs)
+    return list(resblock.convs1) + list(resblock.convs2)
+
+
 class MRF(_HipWeights):
     """Multi-Receptive Field module (models/hifigan.py:89-131): the mean of its
     ResBlocks' outputs on the same input.  Called on its own it runs
-    ``hfg_mrf_forward`` on an MRF handle with this module's state_dict keys."""
+    ``hfg_mrf_forward`` on an MRF handle with this module's state_dict keys.
+    ``resblock="2"`` builds the public release's ResBlock2 blocks."""
 
     def __init__(self, channels: int, resblock_kernel_sizes: List[int] = [3, 7, 11],
                  resblock_dilation_sizes: List[List[int]] = [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
-                 *, precision: Optional[str] = None):
+                 *, precision: Optional[str] = None, resblock: str = "1"):
         super().__init__()
         precision = default_precision() if precision is None else precision
+        self.resblock = str(resblock)
+        _lib._resblock_type(self.resblock)  # "1" or "2"
+        block = ResBlock2 if self.resblock == "2" else ResBlock
         self.channels = channels
         self.resblock_kernel_sizes = list(resblock_kernel_sizes)
         self.resblock_dilation_sizes = [list(d) for d in resblock_dilation_sizes]
         self.resblocks = nn.ModuleList()
         for kernel_size, dilations in zip(resblock_kernel_sizes, resblock_dilation_sizes):
-            self.resblocks.append(ResBlock(channels, kernel_size, tuple(dilations),
-                                           precision=precision))
+            self.resblocks.append(block(channels, kernel_size, tuple(dilations),
+                                        precision=precision))
         self._hip_setup(precision)
 
     def _hip_weight_slots(self):
@@ -261,7 +308,8 @@ class MRF(_HipWeights):
 
     def _hip_new_handle(self, idx):
         cfg = _lib.make_mrf_config(self.channels, self.resblock_kernel_sizes,
-                                   self.resblock_dilation_sizes, precision=self.precision)
+                                   self.resblock_dilation_sizes, precision=self.precision,
+                                   resblock=self.resblock)
         return _lib.Handle(cfg, idx, mrf=True)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -272,7 +320,12 @@ class MRF(_HipWeights):
 class HiFiGANGenerator(_HipWeights):
     """HiFi-GAN Generator, mel [B, n_mels, Tfrm] → wav [B, 1, T_wav] on MI355X.
 
-    Same constructor as models/hifigan.py:149-158.
+    Same constructor as models/hifigan.py:149-158, plus two keyword-only arguments for the
+    public HiFi-GAN release's Generator (jik876/hifi-gan), which differs from the reference's
+    in two places: ``resblock="2"`` builds ResBlock2 blocks (the release's V3), and
+    ``final_lrelu_slope=0.01`` is the release's ``F.leaky_relu(x)`` in front of ``conv_post``
+    (every released generator; the reference uses 0.1 there).  See
+    ``checkpoint.generator_from_release_config``.
     """
 
     def __init__(
@@ -286,9 +339,13 @@ class HiFiGANGenerator(_HipWeights):
         debug_shapes: bool = False,
         *,
         precision: Optional[str] = None,
+        resblock: str = "1",
+        final_lrelu_slope: float = 0.1,
     ):
         super().__init__()
         precision = default_precision() if precision is None else precision
+        self.resblock = str(resblock)
+        self.final_lrelu_slope = float(final_lrelu_slope)
         self.n_mels = n_mels
         self.num_kernels = len(resblock_kernel_sizes)
         self.num_upsamples = len(upsample_rates)
@@ -304,7 +361,7 @@ class HiFiGANGenerator(_HipWeights):
             self.ups.append(nn.ConvTranspose1d(in_channels, out_channels, kernel_size=k, stride=u,
                                                padding=(k - u) // 2))
             self.mrfs.append(MRF(out_channels, resblock_kernel_sizes, resblock_dilation_sizes,
-                                 precision=precision))
+                                 precision=precision, resblock=self.resblock))
         final_channels = upsample_initial_channel // (2 ** self.num_upsamples)
         self.conv_post = nn.Conv1d(final_channels, 1, kernel_size=7, stride=1, padding=3)
 
@@ -321,7 +378,9 @@ class HiFiGANGenerator(_HipWeights):
         committed to the handle, the module's own parameters untouched — activations
         still split: the reference model with bf16-cast weights, to 1e-4).  Applies to
         the MRF / ResBlock submodules too."""
-        self._hfg_cfg = _lib.make_config(*self._hfg_args, precision=precision)
+        self._hfg_cfg = _lib.make_config(*self._hfg_args, precision=precision,
+                                         resblock=self.resblock,
+                                         final_lrelu_slope=self.final_lrelu_slope)
         for m in self.modules():
             if isinstance(m, _HipWeights):
                 m.precision = precision
@@ -459,10 +518,7 @@ class HiFiGANGenerator(_HipWeights):
             rate *= u
             best = 0
             for rb in mrf.resblocks:
-                s = 0
-                for c1, c2 in zip(rb.convs1, rb.convs2):
-                    s += c1.padding[0] + c2.padding[0]
-                best = max(best, s)
+                best = max(best, sum(conv.padding[0] for conv in _block_convs(rb)))
             halo += best / rate
         halo += 3.0 / rate  # conv_post k=7
         return int(halo) + 1
@@ -473,9 +529,7 @@ class HiFiGANGenerator(_HipWeights):
             nn.utils.remove_weight_norm(layer)
         for mrf in self.mrfs:
             for resblock in mrf.resblocks:
-                for conv in resblock.convs1:
-                    nn.utils.remove_weight_norm(conv)
-                for conv in resblock.convs2:
+                for conv in _block_convs(resblock):
                     nn.utils.remove_weight_norm(conv)
 
     def apply_weight_norm(self):
@@ -484,9 +538,7 @@ class HiFiGANGenerator(_HipWeights):
             nn.utils.weight_norm(layer)
         for mrf in self.mrfs:
             for resblock in mrf.resblocks:
-                for conv in resblock.convs1:
-                    nn.utils.weight_norm(conv)
-                for conv in resblock.convs2:
+                for conv in _block_convs(resblock):
                     nn.utils.weight_norm(conv)
 
 
@@ -505,7 +557,8 @@ class HiFiGAN(nn.Module):
                  resblock_dilation_sizes: List[List[int]] = [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
                  msd_use_spectral_norm: bool = False, mpd_periods: List[int] = [2, 3, 5, 7, 11],
                  mpd_use_spectral_norm: bool = False, debug_shapes: bool = False, *,
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None, resblock: str = "1",
+                 final_lrelu_slope: float = 0.1):
         super().__init__()
         self.debug_shapes = debug_shapes or os.getenv("DEBUG_SHAPES", "0") == "1"
         self.generator = HiFiGANGenerator(
@@ -514,7 +567,7 @@ class HiFiGAN(nn.Module):
             upsample_initial_channel=upsample_initial_channel,
             resblock_kernel_sizes=resblock_kernel_sizes,
             resblock_dilation_sizes=resblock_dilation_sizes, debug_shapes=debug_shapes,
-            precision=precision)
+            precision=precision, resblock=resblock, final_lrelu_slope=final_lrelu_slope)
         self.msd = None
         self.mpd = None
 

@@ -42,6 +42,24 @@ NONEXACT = GenConfig(upsample_rates=[5, 5, 4, 2], upsample_kernel_sizes=[10, 10,
 PRESETS = {"v1": V1, "v2star": V2STAR, "nonexact": NONEXACT}
 
 
+@dataclass
+class ReleaseConfig(GenConfig):
+    """A generator of the public HiFi-GAN release (jik876/hifi-gan ``config_v*.json``): the
+    ``GenConfig`` lists plus the two places where its Generator differs from the reference's,
+    both keyword-only arguments of this package's ``HiFiGANGenerator``."""
+    resblock: str = "1"
+    final_lrelu_slope: float = 0.01
+
+
+# the release's config_v3.json: ResBlock2 blocks, 256 initial channels, three upsamplers
+RELEASE_V3 = ReleaseConfig(upsample_rates=[8, 8, 4], upsample_kernel_sizes=[16, 16, 8],
+                           upsample_initial_channel=256, resblock_kernel_sizes=[3, 5, 7],
+                           resblock_dilation_sizes=[[1, 2], [2, 6], [3, 12]], resblock="2")
+# (kept out of PRESETS: that table mirrors the reference-architecture presets of the tests'
+# own generator)
+RELEASE_PRESETS = {"release_v3": RELEASE_V3}
+
+
 def param_specs(cfg: GenConfig) -> List[Tuple[str, Tuple[int, ...], int]]:
     """[(state_dict key, shape, fan_in)] in the reference's state_dict order."""
     specs = []
@@ -60,7 +78,9 @@ def param_specs(cfg: GenConfig) -> List[Tuple[str, Tuple[int, ...], int]]:
         ch = c0 >> (i + 1)
         for j, (kr, dils) in enumerate(zip(cfg.resblock_kernel_sizes,
                                            cfg.resblock_dilation_sizes)):
-            for which in ("convs1", "convs2"):
+            # ResBlock2 (ReleaseConfig.resblock "2"): one conv per dilation, "convs.{m}"
+            for which in (("convs",) if getattr(cfg, "resblock", "1") == "2"
+                          else ("convs1", "convs2")):
                 for m in range(len(dils)):
                     conv(f"mrfs.{i}.resblocks.{j}.{which}.{m}", ch, ch, kr)
     conv("conv_post", 1, c0 >> len(cfg.upsample_rates), 7)
@@ -89,12 +109,15 @@ def layer_streaming_bytes_per_frame(cfg: GenConfig) -> int:
     c_prev = c0
     n_res = len(cfg.resblock_kernel_sizes)
     pairs = sum(len(d) for d in cfg.resblock_dilation_sizes)
+    # passes over C*L per dilation: a pair is conv1 in + out, conv2 in + out + residual; a
+    # ResBlock2 conv is in + out + residual
+    per_dil = 3 if getattr(cfg, "resblock", "1") == "2" else 5
     for i, u in enumerate(cfg.upsample_rates):
         c = c0 >> (i + 1)
         floats += c_prev * rate                            # ups in
         rate *= u
         floats += c * rate                                 # ups out
-        floats += (5 * pairs + 2 * (n_res - 1)) * c * rate  # MRF
+        floats += (per_dil * pairs + 2 * (n_res - 1)) * c * rate  # MRF
         c_prev = c
     floats += c_prev * rate + rate                         # conv_post in + out
     return 4 * floats
