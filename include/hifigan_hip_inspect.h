@@ -39,6 +39,15 @@ int hfg_debug_layer_exponent(hfg_handle* h, const char* mod, int* ew);
 int hfg_debug_packed_resblock(hfg_handle* h, int stage, int j, float* out, size_t cap,
                               int64_t* info);
 
+/* The handle's plan as JSON in buf (NUL-terminated): per layer its kernel path, tile,
+ * packings and packed-buffer offsets; per stage its thin-MRF launch; per ResBlock its
+ * whole-block launch (window, halo, split, fused conv_post); the packed image's length in
+ * floats and the sha256 of its bytes.  Everything the launch code reads from the plan, so
+ * the host suite can pin it (tests/golden/plan_index.json).  Host-only handles included;
+ * commits pending weights first and returns that commit's error.  HFG_EINVAL when buflen
+ * is too small. */
+int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen);
+
 /* A Generator forward (one stream) that also copies the stage outputs the
  * reference's forward passes through (models/hifigan.py:238-251) into
  * caller-owned device buffers: taps[0] <- conv_pre [B][C0][T], taps[1 + 2i] <-
@@ -56,10 +65,12 @@ int hfg_forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, floa
  * UPS_FRAMES 1|2, SPLIT 1|2, RB_PERSIST 0..2, DEBUG_FLAGS (ablation builds), MEL_DFT 0|1,
  * AREG_TALL 0|1.
  * set: HFG_EINVAL for an unknown knob or a value out of range.  clear: one knob, or all
- * with knob == NULL.  get: 1 and *value if the knob is overridden, 0 if not. */
+ * with knob == NULL.  get: 1 and *value if the knob is overridden, 0 if not.
+ * knob: the name of knob i of the library's table, NULL past its end. */
 int hfg_debug_schedule_set(const char* knob, int value);
 int hfg_debug_schedule_clear(const char* knob);
 int hfg_debug_schedule_get(const char* knob, int* value);
+const char* hfg_debug_schedule_knob(int i);
 
 /* Sustained matrix-core rate of GPU `device` under a full-chip load (csrc/probe.hip):
  * 2 blocks x 4 waves per CU issue independent MFMAs back to back on random operands

@@ -31,11 +31,36 @@ def header_symbols():
 def test_library_exports_every_header_symbol(pkg):
     lib = pkg.load_library()
     syms = header_symbols()
-    assert len(syms) == 43
+    assert len(syms) == 45
     for s in sorted(syms):
         assert hasattr(lib, s), f"missing export {s}"
     assert set(syms) == set(pkg._lib.SIGNATURES), "ctypes signatures out of sync with headers"
     assert b"gfx950" in lib.hfg_version()
+
+
+def test_schedule_knob_names_come_from_the_library(pkg):
+    """hfg_debug_schedule_knob lists the library's own knob table: every name it exports is
+    accepted by hfg_debug_schedule_set (over the range its error message states), and the
+    knobs read outside the generator's planner (MEL_DFT) or added last (AREG_TALL) are there,
+    so schedule_overrides() cannot miss a knob."""
+    lib = pkg.load_library()
+    names = pkg._lib.schedule_knobs()
+    assert lib.hfg_debug_schedule_knob(len(names)) is None
+    assert lib.hfg_debug_schedule_knob(-1) is None
+    assert len(set(names)) == len(names) >= 11
+    assert {"MEL_DFT", "AREG_TALL"} <= set(names)
+    try:
+        for k in names:
+            assert lib.hfg_debug_schedule_set(k.encode(), 2 ** 31 - 1) == -22
+            lo, hi = map(int, re.search(r"out of range \[(-?\d+), (-?\d+)\]",
+                                        lib.hfg_last_error().decode()).groups())
+            for v in (lo, hi):
+                assert lib.hfg_debug_schedule_set(k.encode(), v) == 0, (k, v)
+            assert pkg.schedule_overrides()[k] == hi
+        assert sorted(pkg.schedule_overrides()) == sorted(names)
+    finally:
+        pkg.schedule_clear()
+    assert pkg.schedule_overrides() == {}
 
 
 def host_handle(pkg, cfg, precision="fp32"):

@@ -190,7 +190,7 @@ def test_profiling_summary(pkg, v1, dev):
     # k = 7 / 11 ResBlocks layer by layer (6 launches each), the other ResBlocks one whole-
     # ResBlock launch each (two for the split k = 11 ones at C = 32 / 64); a small forward
     # runs its MRFs' ResBlocks on concurrent streams and adds one mrf_combine launch per such
-    # stage (hifigan_capi.cpp run_mrf); the mel's scale slot comes from one absmax launch
+    # stage (forward.cpp run_mrf); the mel's scale slot comes from one absmax launch
     assert gen.precision == "f16x3"
     combine = prof.get("mrf_combine", {"launches": 0})["launches"]
     assert prof.get("absmax", {"launches": 0})["launches"] == 1, sorted(prof)

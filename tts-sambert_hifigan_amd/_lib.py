@@ -190,6 +190,7 @@ SIGNATURES = {
     "hfg_debug_layer_exponent": (c_int, [c_void_p, c_char_p, POINTER(c_int)]),
     "hfg_debug_packed_resblock": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), c_size_t,
                                           POINTER(c_int64)]),
+    "hfg_debug_plan": (c_int, [c_void_p, c_char_p, c_size_t]),
     "hfg_mrf_create": (c_int, [POINTER(HfgMrfConfig), c_int, POINTER(c_void_p)]),
     "hfg_mrf_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
     "hfg_mrf_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
@@ -203,6 +204,7 @@ SIGNATURES = {
     "hfg_debug_schedule_set": (c_int, [c_char_p, c_int]),
     "hfg_debug_schedule_clear": (c_int, [c_char_p]),
     "hfg_debug_schedule_get": (c_int, [c_char_p, POINTER(c_int)]),
+    "hfg_debug_schedule_knob": (c_char_p, [c_int]),
     "hfg_mel_last_error": (c_char_p, []),
     "hfg_mel_create": (c_int, [POINTER(HfgMelConfig), c_int, POINTER(c_void_p)]),
     "hfg_mel_destroy": (None, [c_void_p]),
@@ -288,12 +290,20 @@ def schedule_clear(knob: Optional[str] = None):
     check(load_library().hfg_debug_schedule_clear(None if knob is None else knob.encode()))
 
 
+def schedule_knobs() -> list:
+    """The names of the library's schedule knobs (hfg_debug_schedule_knob)."""
+    lib = load_library()
+    names = []
+    while (name := lib.hfg_debug_schedule_knob(len(names))) is not None:
+        names.append(name.decode())
+    return names
+
+
 def schedule_overrides() -> dict:
     """The overrides in force, {knob: value}."""
     lib = load_library()
     out = {}
-    for k in ("FUSED_RB", "FUSE_POST", "RB_SPLIT", "SMALL_TILE", "RB_CONC", "UPS_FRAMES", "SPLIT",
-              "RB_PERSIST", "DEBUG_FLAGS", "MEL_DFT", "AREG_TALL"):
+    for k in schedule_knobs():
         v = c_int(0)
         if lib.hfg_debug_schedule_get(k.encode(), ctypes.byref(v)) == 1:
             out[k] = v.value
@@ -408,6 +418,13 @@ class Handle:
         import json
         buf = ctypes.create_string_buffer(1 << 16)
         check(self.lib.hfg_profile_summary(self.ptr, buf, len(buf)))
+        return json.loads(buf.value.decode())
+
+    def plan(self) -> dict:
+        """The handle's plan and packed-image hash (hfg_debug_plan)."""
+        import json
+        buf = ctypes.create_string_buffer(1 << 20)
+        check(self.lib.hfg_debug_plan(self.ptr, buf, len(buf)))
         return json.loads(buf.value.decode())
 
     def packed_layer(self, mod: str):

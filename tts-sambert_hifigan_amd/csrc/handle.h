@@ -1,0 +1,264 @@
+// handle.h — what the host orchestration units share: the handle and its plan (layers,
+// whole-ResBlock and thin-stage launches, packed-buffer offsets), the error channel, the
+// schedule-knob table and the device guard.
+//   plan.cpp     config validation, the plan, shapes and workspace sizing (no HIP runtime call)
+//   pack.cpp     weights -> the kernels' packed operand orders (host)
+//   forward.cpp  the launch schedule, the weight upload
+//   hifigan_capi.cpp  the C ABI (include/hifigan_hip.h, hifigan_hip_inspect.h)
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/hifigan_hip.h"
+#include "../../include/hifigan_hip_inspect.h"
+#include "kernels.h"
+
+namespace hfg_host {
+
+// the calling thread's hfg_last_error text; returns code
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int hip_fail(hipError_t e, const char* what);
+
+// Schedule overrides for A/B runs and the parity suites (hfg_debug_schedule_set): a
+// process-wide table read when a handle is created.  The library reads no environment
+// variable for its schedule, so a serving process runs the default schedule whatever it
+// inherits.  Each knob: its valid range and what it selects.
+struct SchedKnob {
+  const char* name;
+  int lo, hi;
+};
+constexpr SchedKnob kSchedKnobs[] = {
+    {"FUSED_RB", 0, 1},     // whole-ResBlock kernels (0: layer by layer)
+    {"FUSE_POST", 0, 1},    // conv_post + tanh inside the last C = 32 ResBlock launch
+    {"RB_SPLIT", 0, 1},     // k = 11 whole-ResBlock launches split in two
+    {"SMALL_TILE", -1, 1},  // small-grid tile: -1 auto, 0 never, 1 always
+    {"RB_CONC", -1, 1},     // concurrent ResBlocks of small forwards: -1 auto, 0 off, 1 on
+    {"UPS_FRAMES", 1, 2},   // output-frame upsampler: 1 when its grid fills the chip, 2 always
+    {"SPLIT", 1, 2},        // batch halves on 2 HIP streams (1: one stream)
+    {"RB_PERSIST", 0, 2},   // persistent C = 64 ResBlock grids: 0 off, 1 n_CU / 2, 2 n_CU
+    {"DEBUG_FLAGS", 0, 1 << 30},  // kernel ablation bits (-DHFG_ABLATE=1 builds only)
+    {"MEL_DFT", 0, 1},      // mel: the DFT-GEMM path instead of the FFT (mel_capi.cpp)
+    {"AREG_TALL", 0, 1},    // 256-row layers on the 256x128 AREG tile (6) instead of tile 5
+};
+// the override of `knob` into *v if one is set (else *v is left alone)
+void sched_apply(const char* knob, int* v);
+void sched_apply(const char* knob, bool* v);
+
+enum LayerKind { L_CONV, L_UPS, L_POST };
+
+// One packing of a layer's weights and per-row biases for one tile of its kernel: offsets
+// and lengths in floats into the packed buffer.
+struct Packing {
+  int tile, m_tiles, n_chunks;
+  size_t w_off, w_len, b_off, b_len;
+};
+
+struct Layer {
+  LayerKind kind;
+  std::string mod;   // state_dict module prefix
+  int C_in, C_out, k, dil, pad;
+  int s, p;          // ConvTranspose1d stride / padding
+  int M, KT, CK;     // GEMM view
+  int prec;          // 0: fp32 MFMA kernel, 1: split-precision kernel (bf16x3 / f16x3)
+  int ew = 0;        // f16x3: power-of-two exponent of this layer's weight packing
+  // [0]: the layer's own tile; [1]: split-precision layers' second packing for the small-grid
+  // tile (kBf16x3SmallTile), tile -1: none
+  Packing pk[2] = {{0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0}};
+  // bf16x3 upsamplers with k = 2u: the output-frame kernel (ups_bf16x3.hip) on its own
+  // packing, -1: none
+  int ups_cfg = -1, m_tiles_f = 0;
+  size_t wf_off = 0, bf_off = 0;
+};
+
+// f16x3, bf16x3 and bf16w run the split-operand MFMA kernels (f16x3 and bf16w in the f16
+// format with power-of-two scales, bf16x3 in the bf16 format: bf16x3_common.h)
+inline bool split_dtype(int dtype) {
+  return dtype == HFG_DTYPE_F16X3 || dtype == HFG_DTYPE_BF16X3 || dtype == HFG_DTYPE_BF16W;
+}
+
+struct Param {
+  std::vector<int64_t> shape;
+  std::vector<float> data;
+  bool set = false;
+};
+
+struct ProfRec {
+  const char* label;
+  double flop, bytes;
+  hipEvent_t e0, e1;
+  int fwd, part, seq;  // forward call, batch half (0/1), launch index inside that half
+};
+
+// One ResBlock run by resblock_bf16x3 (whole block per launch): its packed A stream
+// [wave_m][conv][group][tap][plane][lane][8] and biases [conv][C] in the packed buffer.
+struct RbFused {
+  std::vector<int> convs;     // layer indices in execution order conv1_0, conv2_0, conv1_1, ...
+  bool fused = false;         // this ResBlock runs as one resblock_bf16x3 launch
+  int kt = 0, halo = 0, W = 0, nwin = 0, wm = 1;  // window columns, row tiles per wave
+  // split into two launches (convs [0, split) then [split, n)): each part's window pays
+  // only its own receptive-field halo; the first writes x to scratch (0: one launch)
+  int split = 0;
+  int halo_p[2] = {0, 0}, W_p[2] = {0, 0};
+  // the network's last MRF write may carry conv_post + tanh (forward.cpp, post_fusable): its
+  // last launch is then exact on conv_post's radius more on either side
+  bool post = false;
+  int halo_post = 0, W_post = 0;
+  size_t w_off = 0, w_len = 0, b_off = 0, b_len = 0;  // in floats
+};
+
+struct Stage {
+  int C = 0;                  // channels of this stage's MRF
+  int conv_ups = -1;          // index of the ups layer (-1 in an MRF-only handle)
+  std::vector<int> conv1;     // [j*n_dil + m]
+  std::vector<int> conv2;
+  std::vector<RbFused> rbs;   // per ResBlock: whole-block launch or layer by layer
+  // thin stage (C <= 16): the whole MRF in one mrf_thin launch (packed-fp32 VALU)
+  bool thin = false;
+  std::vector<int> thin_convs;   // layer indices: conv1_0, conv2_0, conv1_1, ... per ResBlock
+  std::vector<int> thin_conv0;   // ResBlock j runs thin_convs[thin_conv0[j] .. thin_conv0[j+1])
+  std::vector<int> thin_halo;    // per ResBlock receptive-field radius
+  std::vector<size_t> thin_w_off;  // per conv, floats into the packed buffer ([tap][ci][co])
+  size_t thin_b_off = 0;           // [conv][C]
+  // bf16x3: the MFMA kernel's A stream [conv][step][plane][lane][8] (mrf_thin_mfma.hip)
+  bool thin_mfma = false;
+  size_t thin_m_off = 0;           // floats into the packed buffer
+  size_t thin_m_bytes = 0;
+  std::vector<int> thin_m_conv;    // byte offset of each conv inside the stream
+};
+
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    if (dev < 0) return;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+}  // namespace hfg_host
+
+struct hfg_handle {
+  hfg_config cfg;
+  int device;  // -1: host-only handle (validation / packing inspection)
+  // MRF-only handle (hfg_mrf_create): one stage of ResBlocks keyed "resblocks.{j}.*"
+  // (the MRF module's own state_dict), no conv_pre / ups / conv_post
+  bool mrf_only = false;
+  // one forward at a time per handle: the split stream, its fork/join events and the
+  // profiling records are shared state (ctypes releases the GIL around the call)
+  std::recursive_mutex mu;
+  std::vector<hfg_host::Layer> layers;
+  int conv_pre = -1, conv_post = -1;
+  std::vector<hfg_host::Stage> stages;
+  std::map<std::string, hfg_host::Param> params;    // "<mod>.weight" / "<mod>.bias"
+  std::map<std::string, hfg_host::Param> wn_parts;  // "<mod>.weight_g" / "<mod>.weight_v"
+  std::vector<std::string> param_order;
+  bool dirty = true;
+  std::vector<float> packed_host;
+  float* packed_dev = nullptr;
+  size_t packed_dev_len = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  bool profiling = false;
+  bool use_fused_rb = true;  // whole-ResBlock kernel for C in {32, 64, 128} (FUSED_RB=0:
+                             // layer by layer; the parity suites compare both schedules)
+  bool rb_split = true;      // whole-ResBlock split in two launches where it cuts >= 10 % of the
+                             // halo recompute (k = 11 in V1; RB_SPLIT=0: one launch)
+  bool fuse_post = true;     // conv_post + tanh inside the last C = 32 ResBlock launch
+                             // (FUSE_POST=0: its own kernel; bitwise the same wav)
+  int ups_frames = 1;        // k = 2u upsamplers on the output-frame kernel: 1 when its grid
+                             // fills the chip, 2 always (UPS_FRAMES; the polyphase
+                             // conv1d_bf16x3 path gives the bitwise same result)
+  int fmt = 0;               // split format of the split kernels (bf16x3_common.h)
+  int np = 3;                // MFMA products per multiply-add: 3, or 2 (bf16w: lo(w) = 0)
+  int small_tile = -1;       // small-grid tile: -1 auto (grid < kSmallGridBlocks), 0 never,
+                             // 1 always (SMALL_TILE; bitwise invisible)
+  int dbg_flags = 0;  // DEBUG_FLAGS (kernel ablations, -DHFG_ABLATE=1 builds only)
+  // RB_PERSIST (default 2): persistent grids for the one-block-per-CU ResBlock launches
+  int rb_persist = 2;
+  // AREG_TALL: layers whose rows are a multiple of 256 on the 256x128 AREG tile (6): each input
+  // window staged once per 128 output columns instead of once per m-tile (bitwise tile 5)
+  int areg_tall = 1;
+  int n_cu = 256;      // compute units of the device (hipDeviceAttributeMultiprocessorCount)
+  int halves = 1;      // batch halves of the running forward (2: two streams share the CUs)
+  // batch split over two HIP streams (SPLIT=1 disables): the two halves' launches
+  // overlap, so one half's ramp-down / epilogue tail runs beside the other's main loops
+  int split = 2;
+  static constexpr int64_t kSplitMinFrames = 4096;  // batch frames from which a forward runs as
+                                                    // two halves on two streams
+  hipStream_t aux = nullptr;
+  hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+  // concurrent ResBlocks of small forwards (RB_CONC: -1 auto, 0 off, 1 whenever the
+  // workspace allows): per batch part, aux streams for ResBlocks 1.. and their events
+  int rb_conc = -1;
+  hipStream_t rb_aux[2][HFG_MAX_RES] = {};
+  hipEvent_t rb_fork[2] = {};
+  hipEvent_t rb_join[2][HFG_MAX_RES] = {};
+  int fwd_count = 0;
+  std::vector<hfg_host::ProfRec> prof;
+  std::vector<hipEvent_t> event_pool;
+};
+
+namespace hfg_host {
+
+// ---- plan.cpp ---------------------------------------------------------------
+int validate_config(const hfg_config* c);
+// Apply the schedule knobs to a handle whose cfg / mrf_only / device are set and build its
+// plan: layers, stages, packed-buffer offsets.  HFG_EINVAL when a layer's taps x dilation
+// is beyond every kernel's staging limits.
+int plan_handle(hfg_handle* h);
+
+struct Shapes {
+  std::vector<int64_t> L;  // L[0] = T, L[i+1] = length after stage i
+  int64_t buf_elems;       // per-buffer elements (all B items)
+  int64_t item_elems;      // largest per-item activation (max over stages of C * L)
+};
+Shapes shapes_for(const hfg_handle* h, int64_t B, int64_t T);
+size_t lens_table_bytes(const hfg_handle* h, int64_t B);
+bool stage_conc(const hfg_handle* h, const Stage& st, int64_t B, int64_t L);
+int n_bufs(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok);
+int n_slots(const hfg_handle* h);
+size_t slots_bytes(const hfg_handle* h, int64_t B);
+size_t ws_part_bytes(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok = false);
+bool split_batch(const hfg_handle* h, int64_t B, int64_t T);
+size_t ws_bytes_for(const hfg_handle* h, int64_t B, int64_t T);
+size_t mrf_ws_bytes(const hfg_handle* h, int64_t B, int64_t L);
+
+// ---- pack.cpp ---------------------------------------------------------------
+// Every weight set -> h->packed_host (HFG_EAGAIN while one is missing); sets Layer::ew.
+int pack_weights(hfg_handle* h);
+
+// ---- forward.cpp ------------------------------------------------------------
+// pack_weights, then (device handles) the upload; clears h->dirty
+int do_commit(hfg_handle* h);
+void recycle_prof(hfg_handle* h);
+// What every forward entry holds while it runs: the handle's lock and its device.
+struct ForwardScope {
+  std::lock_guard<std::recursive_mutex> lk;
+  DeviceGuard g;
+  explicit ForwardScope(hfg_handle* h) : lk(h->mu), g(h->device) {}
+  // after the entry's own argument checks: the device is current, pending weights committed
+  int ready(hfg_handle* h) {
+    if (!g.ok) return fail(HFG_ENODEV, "hipSetDevice(%d) failed", h->device);
+    return h->dirty ? do_commit(h) : HFG_OK;
+  }
+};
+int forward_split(hfg_handle* h, const float* mel, int64_t B, int64_t T,
+                  const hfg_forward_opts* o, float* wav, int64_t out_len, void* ws, size_t ws_len,
+                  hipStream_t stream);
+// one stream, with the inspection taps of hfg_forward_taps
+int forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, float* wav,
+                 int64_t out_len, void* ws, size_t ws_len, float* const* taps, hipStream_t stream);
+int mrf_run(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, float* y, void* ws,
+            size_t ws_bytes, hipStream_t stream);
+
+}  // namespace hfg_host
