@@ -24,6 +24,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "epilogue.h"
 #include "kernels.h"
 
@@ -60,6 +62,28 @@ __device__ __forceinline__ floatx4_ mfma16(const bf16x8& a, const bf16x8& b, con
   else
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(halfx8, a),
                                                   __builtin_bit_cast(halfx8, b), c, 0, 0, 0);
+}
+
+// One split-precision multiply-add, acc += a * b with a = ah + al (weights), b = bh + bl
+// (activations): lo(a)*hi(b) (NP = 3 only: the weights' lo plane is zero for bf16-valued
+// weights, NP 2), then hi(a)*lo(b), then hi(a)*hi(b); lo*lo (2^-16 relative) is dropped.
+// Every split kernel accumulates the terms in THIS order, smallest first — that, with the
+// (channel group, tap) order of the k-steps, is what makes their results bitwise comparable
+// (tile 3 / 4 / 5 / 6, whole-ResBlock and layer launches, the two upsamplers).  The
+// accumulator picks the instruction: floatx16 the 32x32x16 MFMA, floatx4_ the 16x16x32 one.
+template <int NP, int FMT, typename Acc>
+__device__ __forceinline__ void mma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
+                                     const bf16x8& bl, Acc& acc) {
+  static_assert(NP == 2 || NP == 3, "products per multiply-add");
+  auto mfma = [](const bf16x8& a, const bf16x8& b, const Acc& c) {
+    if constexpr (std::is_same_v<Acc, floatx16>)
+      return mfma32<FMT>(a, b, c);
+    else
+      return mfma16<FMT>(a, b, c);
+  };
+  if constexpr (NP == 3) acc = mfma(al, bh, acc);
+  acc = mfma(ah, bl, acc);
+  acc = mfma(ah, bh, acc);
 }
 
 // hi = fmt(a), lo = fmt(a - hi) of two values (a - hi is exact in fp32), as bit patterns.
@@ -154,7 +178,9 @@ __device__ __forceinline__ float div_fast(float x, float d, float rcp) {
 // HFG_PRIO (round 6): a wave raises its issue priority for its matrix phase (s_setprio 1) and
 // drops it for staging / epilogue work, so a co-resident wave of ANOTHER block (2 blocks per CU)
 // that is in its MFMA loop wins the SIMD's issue arbitration over this wave's VALU burst
-// (MI355X_MICROARCH.md "Two waves per SIMD", items 2 and 4)
+// (MI355X_MICROARCH.md "Two waves per SIMD", items 2 and 4).  The ResBlock and upsampler
+// kernels bracket each matrix phase; the AREG path of conv1d_bf16x3 interleaves its staging
+// into the MFMA stream and holds priority 1 over its whole channel-group loop
 #ifndef HFG_PRIO
 #define HFG_PRIO 1
 #endif

@@ -30,6 +30,7 @@
 #include "bf16x3_common.h"
 #include "epilogue.h"
 #include "kernels.h"
+#include "launch.h"
 
 #ifndef HFG_AREG_AD
 #define HFG_AREG_AD 2
@@ -60,11 +61,6 @@ namespace hfg {
 constexpr int kCvTsSlots = 16, kCvTsBlocks = 8192, kCvTsRegions = 12;
 __device__ uint64_t g_cv_ts[kCvTsRegions * kCvTsBlocks * kCvTsSlots];
 #endif
-
-namespace {
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-}  // namespace
 
 template <int KT_, int TPC, int WAVES_M, int WAVES_N, int WM, int WN, int WD, bool UPS, int NP,
           bool AREG, int FMT>
@@ -261,7 +257,7 @@ conv1d_bf16x3(const ConvParams p) {
         } else
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
-          floatx2 a;
+          floatx2_ a;
           if (AREG || xfull) {
             a[0] = fmaxf(xv[q][e] * xs1[q], xv[q][e] * xs2[q]);
             a[1] = fmaxf(xv[q][e + 1] * xs1[q], xv[q][e + 1] * xs2[q]);
@@ -274,7 +270,7 @@ conv1d_bf16x3(const ConvParams p) {
             }
             if constexpr (FMT == kFmtF16) a = a * sx;
           }
-          bf16x2 hh, ll;
+          bf16x2_ hh, ll;
           split2<FMT>(a, hh, ll);
           h[e] = hh[0];
           h[e + 1] = hh[1];
@@ -327,12 +323,7 @@ conv1d_bf16x3(const ConvParams p) {
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
-      for (int k = 0; k < WN; ++k) {
-        if constexpr (NP == 3)  // the weights' lo plane (zero for bf16-valued weights: NP 2)
-          acc[i][k] = mfma32<FMT>(f.al[i], f.bh[k], acc[i][k]);
-        acc[i][k] = mfma32<FMT>(f.ah[i], f.bl[k], acc[i][k]);
-        acc[i][k] = mfma32<FMT>(f.ah[i], f.bh[k], acc[i][k]);
-      }
+      for (int k = 0; k < WN; ++k) mma3<NP, FMT>(f.ah[i], f.al[i], f.bh[k], f.bl[k], acc[i][k]);
   };
 
   // One tap of the 64x128-per-wave tile with the B fragments streamed per column tile
@@ -358,12 +349,7 @@ conv1d_bf16x3(const ConvParams p) {
     for (int k = 0; k < WN; ++k) {
       if (k + 1 < WN) ldb(k + 1);
 #pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        if constexpr (NP == 3)
-          acc[i][k] = mfma32<FMT>(al[i], bh[k & 1], acc[i][k]);
-        acc[i][k] = mfma32<FMT>(ah[i], bl[k & 1], acc[i][k]);
-        acc[i][k] = mfma32<FMT>(ah[i], bh[k & 1], acc[i][k]);
-      }
+      for (int i = 0; i < WM; ++i) mma3<NP, FMT>(ah[i], al[i], bh[k & 1], bl[k & 1], acc[i][k]);
     }
   };
   // sched_group_barrier pattern for tap_stream + staging work in one basic block: the A
@@ -484,12 +470,8 @@ conv1d_bf16x3(const ConvParams p) {
       for (int k = 0; k < WN; ++k) {
         if (k + 1 < WN || pre_out) ldb(Xh, tap, k + 1);  // k + 1 == WN: tap + 1, tile 0
 #pragma unroll
-        for (int i = 0; i < WM; ++i) {
-          if constexpr (NP == 3)
-            acc[i][k] = mfma32<FMT>(a[1][i], bh[k & 1], acc[i][k]);
-          acc[i][k] = mfma32<FMT>(a[0][i], bl[k & 1], acc[i][k]);
-          acc[i][k] = mfma32<FMT>(a[0][i], bh[k & 1], acc[i][k]);
-        }
+        for (int i = 0; i < WM; ++i)
+          mma3<NP, FMT>(a[0][i], a[1][i], bh[k & 1], bl[k & 1], acc[i][k]);
       }
     };
     // one tap's interleave: B(0) first (unless the previous tap read it), then per MFMA up to
@@ -513,6 +495,10 @@ conv1d_bf16x3(const ConvParams p) {
     };
     load_a(a0, 0, 0);
     if constexpr (AD == 2) load_a(a1, 0, 1);
+    // raised for the whole channel-group loop, not per matrix phase as in the ResBlock and
+    // upsampler kernels: this path has no separate staging phase to drop it for (load_x and
+    // store_x are interleaved into the taps' MFMA streams, pin_regs), so its staging loads,
+    // conversions and LDS writes run at priority 1 too; it drops for the epilogue
     prio_mfma();
     for (int g = 0; g < NG; ++g) {
       const __bf16* Xh = Xbuf0 + (g & 1) * xbuf;
@@ -722,7 +708,7 @@ conv1d_bf16x3(const ConvParams p) {
       const int rb = mt * MT + wave_m * 32 * WM + i * 32 + 4 * half;  // row of r = 0
       float bv[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bv[r] = p.bias[rb + (r & 3) + 8 * (r >> 2)];
+      for (int r = 0; r < 16; ++r) bv[r] = p.bias[rb + acc_row(r)];
 #pragma unroll
       for (int k = 0; k < WN; ++k) {
         const int n = n0 + wave_n * 32 * WN + k * 32 + col;
@@ -776,7 +762,7 @@ conv1d_bf16x3(const ConvParams p) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = rb + (r & 3) + 8 * (r >> 2);
+          const int row = rb + acc_row(r);
           if (row >= p.M) continue;
           const int co = co_of(row);
           const int t = n * s_ + (row - co * s_) - p_;
@@ -843,12 +829,11 @@ struct Entry3 {
   int tile;
   bool ups;
   int np, fmt;
-  ConvFn3 fn;
-  char name[112];
+  Instance<ConvParams> inst;
 };
 
 #define HFG3_ENTRY(KT, TILE, UPS, NP, FMT) \
-  { KT, TILE, UPS, NP, FMT, Inst3<KT, TILE, UPS, NP, FMT>::fn(), {0} }
+  { KT, TILE, UPS, NP, FMT, {Inst3<KT, TILE, UPS, NP, FMT>::fn(), {0}} }
 // per tile: bf16x3 (NP 3, bf16), f16x3 (NP 3, f16) and bf16w (NP 2 on the f16 kernels: the
 // bf16-rounded weights are exact f16 halves after their power-of-two scale, lo(w) = 0)
 #define HFG3_VARIANTS(KT, TILE, UPS) \
@@ -895,25 +880,18 @@ hipError_t launch_conv_bf16x3(int tile, int kt, bool ups, int fmt, int np, const
   if (p.dil > kMaxDil || (e->kt == 0 && kt > 16) || (kt - 1) * p.dil > kBf16x3MaxHalo)
     return hipErrorInvalidValue;
   const Bf16x3Cfg& t = kBf16x3Tiles[tile];
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "conv1d_bf16x3<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %d>",
-               e->kt, t.TPC, t.WAVES_M, t.WAVES_N, t.WM, t.WN, t.WD, e->ups ? "true" : "false",
-               e->np, t.AREG ? "true" : "false", e->fmt);
-  }
   size_t lds = bf16x3_lds_bytes(tile, kt, p.dil);
   if (p.epi_lds && !ups)
     lds = std::max(lds, (size_t)t.threads() / 64 * 32 * (32 * t.WN + 8) * sizeof(float));
   // AREG: + the m-tile's bias copy (its kernel instance is compiled for its KT)
   if (t.AREG) lds = (size_t)bf16x3_areg_bias_off(e->kt, t) + (size_t)t.MT() * sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  if (name) *name = e->name;
-  dim3 grid(n_tiles, m_tiles, batch);
-  e->fn<<<grid, dim3(t.threads()), lds, stream>>>(p);
-  return hipGetLastError();
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "conv1d_bf16x3<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %d>", e->kt, t.TPC,
+             t.WAVES_M, t.WAVES_N, t.WM, t.WN, t.WD, e->ups ? "true" : "false", e->np,
+             t.AREG ? "true" : "false", e->fmt);
+  };
+  return launch_instance(e->inst, fmt_name, dim3(n_tiles, m_tiles, batch), dim3(t.threads()), lds,
+                         stream, name, p);
 }
 
 }  // namespace hfg

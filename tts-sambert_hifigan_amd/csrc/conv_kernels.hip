@@ -34,6 +34,7 @@
 
 #include "epilogue.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace hfg {
 
@@ -210,14 +211,14 @@ conv1d_mfma_f32(const ConvParams p) {
       float bv[16];  // batch the bias loads ahead of the scattered stores
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        bv[r] = p.bias[mt * MT + wave_m * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+        bv[r] = p.bias[mt * MT + wave_m * 32 * WM + i * 32 + acc_row(r) + 4 * half];
 #pragma unroll
       for (int k = 0; k < WN; ++k) {
         const int n = n0 + wave_n * 32 * WN + k * 32 + col;
         if (n >= N_b) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = mt * MT + wave_m * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int row = mt * MT + wave_m * 32 * WM + i * 32 + acc_row(r) + 4 * half;
           if (row >= p.M) continue;
           const float v = acc[i][k][r] + bv[r];
           const int co = row / p.ups_s;
@@ -398,12 +399,11 @@ struct Entry {
   int kt;
   int tile;
   bool ups;
-  ConvFn fn;
-  char name[96];  // template-instance name as rocprofv3 prints it
+  Instance<ConvParams> inst;
 };
 
 #define HFG_ENTRY(KT, TILE, UPS) \
-  { KT, TILE, UPS, Inst<KT, TILE, UPS>::fn(), {0} }
+  { KT, TILE, UPS, {Inst<KT, TILE, UPS>::fn(), {0}} }
 
 #define HFG_ENTRIES_KT(KT, UPS) \
   HFG_ENTRY(KT, 0, UPS), HFG_ENTRY(KT, 1, UPS), HFG_ENTRY(KT, 2, UPS)
@@ -429,12 +429,6 @@ hipError_t launch_conv(TileId tile, int kt, bool ups, const ConvParams& p, int n
   if (!e) return hipErrorInvalidValue;
   const TileCfg& t = kTiles[tile];
   const int ck = ck_for(e->kt, tile);
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "conv1d_mfma_f32<%d, %d, %d, %d, %d, %d, %s>", e->kt, t.WM,
-               t.WN, t.WAVES_M, t.WAVES_N, ck, e->ups ? "true" : "false");
-  }
   if ((kt - 1) * p.dil > halo_max(e->kt)) return hipErrorInvalidValue;
   const int xw = t.NTILE() + (kt - 1) * p.dil;
   const size_t stage = (size_t)t.MT() * ck * kt + (((size_t)ck * xw + 3) & ~(size_t)3);
@@ -443,13 +437,12 @@ hipError_t launch_conv(TileId tile, int kt, bool ups, const ConvParams& p, int n
   ConvParams pe = p;
   const size_t epi = sizeof(float) * (size_t)t.threads() / 64 * 32 * (32 * t.WN + 8);
   if (ups || epi > lds) pe.epi_lds = 0;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  if (name) *name = e->name;
-  dim3 grid(n_tiles, m_tiles, batch);
-  e->fn<<<grid, dim3(t.threads()), lds, stream>>>(pe);
-  return hipGetLastError();
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "conv1d_mfma_f32<%d, %d, %d, %d, %d, %d, %s>", e->kt, t.WM, t.WN, t.WAVES_M,
+             t.WAVES_N, ck, e->ups ? "true" : "false");
+  };
+  return launch_instance(e->inst, fmt_name, dim3(n_tiles, m_tiles, batch), dim3(t.threads()), lds,
+                         stream, name, pe);
 }
 
 hipError_t launch_conv_post(const float* x, int64_t x_bs, int C, int L, const float* w,
@@ -461,14 +454,11 @@ hipError_t launch_conv_post(const float* x, int64_t x_bs, int C, int L, const fl
     conv_post4_tanh<<<grid, dim3(256), 0, stream>>>(x, x_bs, C, L, w, bias, wav, lens, slope);
     return hipGetLastError();
   }
-  const size_t lds = conv_post_lds_bytes(C);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(conv_post_tanh)))
-    return err;
-  if (name) *name = "conv_post_tanh";
-  dim3 grid((L + 255) / 256, batch);
-  conv_post_tanh<<<grid, dim3(256), lds, stream>>>(x, x_bs, C, L, w, bias, wav, lens, slope);
-  return hipGetLastError();
+  static auto inst = instance_of(conv_post_tanh);
+  auto fmt_name = [](char* s, size_t n) { snprintf(s, n, "conv_post_tanh"); };
+  return launch_instance(inst, fmt_name, dim3((L + 255) / 256, batch), dim3(256),
+                         conv_post_lds_bytes(C), stream, name, x, x_bs, C, L, w, bias, wav, lens,
+                         slope);
 }
 
 __global__ void stage_lengths_kernel(const int32_t* __restrict__ lens, int B, StageLenParams sp,
@@ -615,7 +605,7 @@ bool fp32_conv_supported(int tile, int kt, int dil) {
   const int ck = ck_for(dkt, tile);
   const int xw = t.NTILE() + (kt - 1) * dil;
   const size_t stage = (size_t)t.MT() * ck * kt + (((size_t)ck * xw + 3) & ~(size_t)3);
-  return sizeof(float) * 2 * stage <= 160 * 1024;
+  return sizeof(float) * 2 * stage <= kMaxLdsBytes;
 }
 
 // Order-independent 32-bit content hash of fp32 tensors (the drop-in module's check that

@@ -20,6 +20,13 @@ namespace hfg {
 
 typedef float floatx16e __attribute__((ext_vector_type(16)));
 
+// Row of accumulator element r (0..15) inside a 32x32 MFMA tile for a lane of half h
+// (h = lane >> 5; the lane's column is lane & 31): four runs of 4 consecutive rows, 8 apart,
+// the upper half-wave's shifted by 4.  The 16x16 tile's 4 elements are the first run.
+__host__ __device__ constexpr int acc_row(int r, int h = 0) {
+  return (r & 3) + 8 * (r >> 2) + 4 * h;
+}
+
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a compile-time loop (a
 // `#pragma unroll` loop around a large body can stay a loop, and an accumulator array it
 // indexes then lives in scratch)
@@ -90,7 +97,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, const float* 
     float bv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      bv[r] = bias[row_base + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+      bv[r] = bias[row_base + i * 32 + acc_row(r, half)];
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
       const int n = n_base + k * 32 + col;
@@ -100,7 +107,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, const float* 
       float v[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row_base + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int row = row_base + i * 32 + acc_row(r, half);
         ok[r] = nok && row < p.M;
         off[r] = ok[r] ? (unsigned)(row * p.N + n) * 4u : 0u;
         v[r] = __builtin_fmaf(acc[i][k][r], sc, bv[r]);
@@ -179,7 +186,7 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, floatx16e
     for (int k = 0; k < WN; ++k)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        stage[((r & 3) + 8 * (r >> 2) + 4 * half) * SROW + k * 32 + col] = acc[i][k][r];
+        stage[(acc_row(r, half)) * SROW + k * 32 + col] = acc[i][k][r];
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's writes are in LDS
     __builtin_amdgcn_wave_barrier();
     constexpr int IT = 32 * C4 / 64;          // float4 per lane
@@ -333,7 +340,7 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
     for (int k = 0; k < WN; ++k)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        stage[((r & 3) + 8 * (r >> 2) + 4 * half) * SROW + k * 32 + col] = acc[i][k][r];
+        stage[(acc_row(r, half)) * SROW + k * 32 + col] = acc[i][k][r];
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's writes are in LDS
     __builtin_amdgcn_wave_barrier();
     ts(8 + 2 * i);

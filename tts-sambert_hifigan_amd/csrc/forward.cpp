@@ -23,7 +23,7 @@ hipError_t ensure_max_lds(const void* fn) {
   if (e != hipSuccess) return e;
   std::lock_guard<std::mutex> lk(setup_mutex());
   if (done.count({fn, dev})) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
   if (e == hipSuccess) done.insert({fn, dev});
   return e;
 }

@@ -1,5 +1,6 @@
-// kernels.h — device-kernel interface shared by the kernels (conv_kernels.hip)
-// and the host orchestration (hifigan_capi.cpp).  No torch types anywhere.
+// kernels.h — device-kernel interface shared by the kernel translation units (*.hip) and
+// the host orchestration (plan.cpp: launch decisions, pack.cpp: weight layouts, forward.cpp:
+// the launch schedule; hifigan_capi.cpp is the C ABI over them).  No torch types anywhere.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,8 @@ namespace hfg {
 // One-time launch setup of a kernel entry, safe across threads and devices:
 // the dynamic-LDS limit is a per-device function attribute, so it is set once per
 // (kernel, device) under a lock; entry names are formatted under the same lock.
+// (forward.cpp; every launcher reaches them through launch_instance, launch.h)
+constexpr size_t kMaxLdsBytes = 160 * 1024;  // LDS of a gfx950 CU: a block's limit
 hipError_t ensure_max_lds(const void* fn);
 std::mutex& setup_mutex();
 
@@ -43,7 +46,7 @@ struct ConvParams {
   int C_in, L_in;
   const int32_t* len_in;   // per-item valid input length (device, [B]) or null = L_in
   const int32_t* len_out;  // per-item valid output length (device, [B]) or null = N / L_out
-  const float* w;    // packed weights (see pack layout in hifigan_capi.cpp)
+  const float* w;    // packed weights (layouts: pack.cpp)
   const float* bias; // per GEMM row m, length >= m_tiles * MT
   float* y;          // output [B][M][N] (regular) or [B][C_out][L_out] (UPS)
   int64_t y_bs;

@@ -19,6 +19,7 @@
 
 #include "../../include/hifigan_hip.h"
 #include "../../include/hifigan_hip_inspect.h"
+#include "kernels.h"
 #include "mel_kernels.h"
 
 namespace {
@@ -230,7 +231,7 @@ int hfg_mel_create(const hfg_mel_config* c, int device, hfg_mel_handle** out) {
   int md = 0;  // 1: the DFT-GEMM path (A/B and fallback tests: hfg_debug_schedule_set)
   hfg_debug_schedule_get("MEL_DFT", &md);
   h->fft = (N & (N - 1)) == 0 && N >= 16 && md == 0 &&
-           hfg::logmel_fft_lds_bytes(N, c->hop_length, h->fpw, c->n_mels) <= 160 * 1024;
+           hfg::logmel_fft_lds_bytes(N, c->hop_length, h->fpw, c->n_mels) <= hfg::kMaxLdsBytes;
   if (!h->fft && !dft_fits) {
     delete h;
     return mfail(HFG_EINVAL, "n_fft / hop too large for the LDS frame tiles");

@@ -13,8 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 
+#include "epilogue.h"
 #include "kernels.h"
+#include "launch.h"
 #include "mel_kernels.h"
 
 namespace hfg {
@@ -71,7 +74,7 @@ stft_power_mfma(const float* __restrict__ wav, int64_t N, int n_fft, int hop, in
     }
     if (bin < n_bins) {
       for (int r = 0; r < 16; ++r) {
-        const int fr = f0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int fr = f0 + acc_row(r, half);
         if (fr < n_frames)
           power[((int64_t)b * n_frames + fr) * n_bins + bin] = re[r] * re[r] + im[r] * im[r];
       }
@@ -291,14 +294,14 @@ hipError_t launch_logmel_fft(const float* wav, int64_t B, int64_t n_samp, int n_
                              const int* band, const float* bw, int n_mels, float eps,
                              int log_mode, float ln_base, float* mel, hipStream_t stream) {
   if (n_fft < 16 || (n_fft & (n_fft - 1)) || fpw < 1) return hipErrorInvalidValue;
-  const size_t lds = logmel_fft_lds_bytes(n_fft, hop, fpw, n_mels);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(logmel_fft))) return err;
+  static auto inst = instance_of(logmel_fft);
+  auto fmt_name = [](char* s, size_t n) { snprintf(s, n, "logmel_fft"); };
   dim3 grid((n_frames + 4 * fpw - 1) / (4 * fpw), (unsigned)B);
-  logmel_fft<<<grid, dim3(256), lds, stream>>>(wav, n_samp, n_fft, hop, n_frames, fpw, window,
-                                               reinterpret_cast<const cd*>(tw), band, bw, n_mels,
-                                               eps, log_mode, ln_base, mel);
-  return hipGetLastError();
+  return launch_instance(inst, fmt_name, grid, dim3(256),
+                         logmel_fft_lds_bytes(n_fft, hop, fpw, n_mels), stream, nullptr, wav,
+                         n_samp, n_fft, hop, n_frames, fpw, window,
+                         reinterpret_cast<const cd*>(tw), band, bw, n_mels, eps, log_mode, ln_base,
+                         mel);
 }
 
 hipError_t launch_stft_power(const float* wav, int64_t B, int64_t N, int n_fft, int hop,

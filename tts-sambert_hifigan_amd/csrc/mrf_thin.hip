@@ -35,11 +35,11 @@
 
 #include "bf16x3_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace hfg {
 
 namespace {
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 // constant address space: block-uniform weight / bias reads become scalar loads (SGPRs)
 typedef __attribute__((address_space(4))) const float cfloat;
 }  // namespace
@@ -76,7 +76,7 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
 
   const float* __restrict__ xb = p.x + (int64_t)b * p.bs;
   // operand <- lrelu(v), zero outside [0, len)
-  auto write_operand = [&](const floatx2 (&v)[C][NP]) {
+  auto write_operand = [&](const floatx2_ (&v)[C][NP]) {
 #pragma unroll
     for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -88,7 +88,7 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
         }
   };
 
-  floatx2 acc[C][NP];
+  floatx2_ acc[C][NP];
   // acc = bias + W_cv * operand
   auto run_conv = [&](int cv) {
     const int kt = p.kt[cv], d = p.dil[cv];
@@ -98,7 +98,7 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
     for (int co = 0; co < C; ++co) {
       const float bv = bc[co];
 #pragma unroll
-      for (int q = 0; q < NP; ++q) acc[co][q] = floatx2{bv, bv};
+      for (int q = 0; q < NP; ++q) acc[co][q] = floatx2_{bv, bv};
     }
     const float* src = op + MARG + cbase - (kt - 1) / 2 * d;
     for (int j = 0; j < kt; ++j, src += d) {
@@ -109,7 +109,7 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
         const float* sg = src + cg * RS;
         // the group's operand reads and scalar weight loads first, one wait, then its
         // CG*C*NP packed FMAs (SMEM returns out of order: any use waits lgkmcnt(0))
-        floatx2 xv[CG][NP];
+        floatx2_ xv[CG][NP];
         float wv[CG][C];
 #pragma unroll
         for (int cc = 0; cc < CG; ++cc) {
@@ -125,7 +125,7 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
         for (int cc = 0; cc < CG; ++cc)
 #pragma unroll
           for (int co = 0; co < C; ++co) {
-            const floatx2 w2{wv[cc][co], wv[cc][co]};
+            const floatx2_ w2{wv[cc][co], wv[cc][co]};
 #pragma unroll
             for (int q = 0; q < NP; ++q)
               acc[co][q] = __builtin_elementwise_fma(xv[cc][q], w2, acc[co][q]);
@@ -134,9 +134,9 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
     }
   };
 
-  floatx2 mrf[C][NP];
+  floatx2_ mrf[C][NP];
   for (int r = 0; r < p.n_res; ++r) {
-    floatx2 xr[C][NP];
+    floatx2_ xr[C][NP];
 #pragma unroll
     for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -201,16 +201,13 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
 
 namespace {
 
-typedef void (*ThinFn)(const ThinParams);
-
 struct EntryThin {
   int C, ncol, nt, wpe;
-  ThinFn fn;
-  char name[48];
+  Instance<ThinParams> inst;
 };
 
 #define HFGTHIN_ENTRY(C_, NCOL_, NT_, WPE_) \
-  { C_, NCOL_, NT_, WPE_, mrf_thin<C_, NCOL_, NT_, WPE_>, {0} }
+  { C_, NCOL_, NT_, WPE_, {mrf_thin<C_, NCOL_, NT_, WPE_>, {0}} }
 
 EntryThin g_entriesThin[] = {HFGTHIN_ENTRY(16, 2, 256, 3), HFGTHIN_ENTRY(8, 4, 256, 3),
                              HFGTHIN_ENTRY(4, 8, 256, 3)};
@@ -248,19 +245,12 @@ hipError_t launch_mrf_thin(int C, const ThinParams& p, int batch, hipStream_t st
       if (p.kt[cv] < 1 || p.dil[cv] < 1 || (p.kt[cv] - 1) / 2 * p.dil[cv] > kThinMarg)
         return hipErrorInvalidValue;
   }
-  const size_t lds = thin_lds_bytes(C);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0]) snprintf(e->name, sizeof(e->name), "mrf_thin<%d, %d, %d, %d>", e->C, e->ncol, e->nt,
-                               e->wpe);
-  }
-  if (name) *name = e->name;
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "mrf_thin<%d, %d, %d, %d>", e->C, e->ncol, e->nt, e->wpe);
+  };
   const int n_tiles = (p.L + p.W - 1) / p.W;
-  e->fn<<<dim3(n_tiles, batch), dim3(e->nt), lds, stream>>>(p);
-  return hipGetLastError();
+  return launch_instance(e->inst, fmt_name, dim3(n_tiles, batch), dim3(e->nt), thin_lds_bytes(C),
+                         stream, name, p);
 }
 
 }  // namespace hfg

@@ -34,13 +34,12 @@
 
 #include "bf16x3_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace hfg {
 
 namespace {
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 }  // namespace
 
@@ -106,10 +105,10 @@ mrf_thin_mfma(const ThinParams p) {
       bf16x4 h, l;
 #pragma unroll
       for (int i = 0; i < 4; i += 2) {
-        floatx2 a;
+        floatx2_ a;
         a[0] = vk[t] ? fmaxf(v[t][i] * sc, v[t][i] * sc1) : 0.f;
         a[1] = vk[t] ? fmaxf(v[t][i + 1] * sc, v[t][i + 1] * sc1) : 0.f;
-        bf16x2 hh, ll;
+        bf16x2_ hh, ll;
         split2<FMT>(a, hh, ll);
         h[i] = hh[0];
         h[i + 1] = hh[1];
@@ -189,10 +188,7 @@ mrf_thin_mfma(const ThinParams p) {
         const int u = s * NCT + t;
         if (t + 1 < NCT) load_b((u + 1) & 1, s, t + 1);
         else if (s + 1 < steps) load_b((u + 1) & 1, s + 1, 0);
-        if constexpr (NP == 3)  // the weights' lo plane (zero for bf16-valued weights)
-          acc[t] = mfma16<FMT>(a1[s], bh[u & 1], acc[t]);
-        acc[t] = mfma16<FMT>(a0[s], bl[u & 1], acc[t]);
-        acc[t] = mfma16<FMT>(a0[s], bh[u & 1], acc[t]);
+        mma3<NP, FMT>(a0[s], a1[s], bh[u & 1], bl[u & 1], acc[t]);
       }
     }
     float bv[4];
@@ -273,18 +269,15 @@ mrf_thin_mfma(const ThinParams p) {
 
 namespace {
 
-typedef void (*ThinMfmaFn)(const ThinParams);
-
 struct EntryThinMfma {
   int C, np, fmt;
-  ThinMfmaFn fn;
-  char name[48];
+  Instance<ThinParams> inst;
 };
 
 // bf16x3 (NP 3, bf16), f16x3 (NP 3, f16), bf16w (NP 2 on the f16 kernel)
-EntryThinMfma g_entriesThinMfma[] = {{16, 3, 0, mrf_thin_mfma<16, 3, 0>, {0}},
-                                     {16, 3, 1, mrf_thin_mfma<16, 3, 1>, {0}},
-                                     {16, 2, 1, mrf_thin_mfma<16, 2, 1>, {0}}};
+EntryThinMfma g_entriesThinMfma[] = {{16, 3, 0, {mrf_thin_mfma<16, 3, 0>, {0}}},
+                                     {16, 3, 1, {mrf_thin_mfma<16, 3, 1>, {0}}},
+                                     {16, 2, 1, {mrf_thin_mfma<16, 2, 1>, {0}}}};
 
 EntryThinMfma* find_thin_mfma(int C, int fmt = 0, int np = 3) {
   for (auto& e : g_entriesThinMfma)
@@ -320,18 +313,12 @@ hipError_t launch_mrf_thin_mfma(int C, int fmt, int np, const ThinParams& p, int
               kThinMarg)
         return hipErrorInvalidValue;
   }
-  const size_t lds = thin_mfma_lds_bytes(C);
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "mrf_thin_mfma<%d, %d, %d>", e->C, e->np, e->fmt);
-  }
-  if (name) *name = e->name;
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "mrf_thin_mfma<%d, %d, %d>", e->C, e->np, e->fmt);
+  };
   const int n_tiles = (p.L + p.W - 1) / p.W;
-  e->fn<<<dim3(n_tiles, batch), dim3(256), lds, stream>>>(p);
-  return hipGetLastError();
+  return launch_instance(e->inst, fmt_name, dim3(n_tiles, batch), dim3(256),
+                         thin_mfma_lds_bytes(C), stream, name, p);
 }
 
 }  // namespace hfg

@@ -41,6 +41,7 @@
 
 #include "bf16x3_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 // diagnostic build only (-DHFG_RB_TIMING=1, profiles/r04): wave 0 of every block stamps the
 // shader clock at the phase boundaries into g_rb_ts (one region per instance and launch half),
@@ -57,8 +58,6 @@ __device__ uint64_t g_rb_ts[kRbTsRegions * kRbTsBlocks * kRbTsSlots];
 #endif
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // conv_post + tanh (models/hifigan.py:254-256) fused into the network's last MRF write (C = 32,
 // one 32-row wave per window slice): the exact final x on the window columns [halo - 3,
@@ -83,7 +82,7 @@ __device__ __forceinline__ void conv_post_tail(const RbParams& p, const floatx16
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float v = xcur[0][k][r];
-      s[((r & 3) + 8 * (r >> 2) + 4 * half) * S + cbase + 32 * k + col + sh] =
+      s[acc_row(r, half) * S + cbase + 32 * k + col + sh] =
           ok[k] ? (v > 0.f ? v : v * slope) : 0.f;
     }
   lds_barrier();
@@ -114,10 +113,10 @@ __device__ __forceinline__ void conv_post_tail(const RbParams& p, const floatx16
 #pragma unroll
           for (int j = 0; j < KP; ++j) acc[o] = fmaf(w[j], v[2 * H + o + j + 1], acc[o]);
       }
-      floatx2 r;
+      floatx2_ r;
 #pragma unroll
       for (int o = 0; o < 2; ++o) r[o] = t + 2 * H + o >= len_b ? 0.f : tanhf(acc[o] + bias);
-      *reinterpret_cast<floatx2*>(wav + t + 2 * H) = r;
+      *reinterpret_cast<floatx2_*>(wav + t + 2 * H) = r;
     }
   };
   if (hq == 0)
@@ -136,19 +135,16 @@ __device__ __forceinline__ void conv_post_tail(const RbParams& p, const floatx16
 
 namespace {
 
-typedef void (*RbFn)(const RbParams);
-
 struct EntryRb {
   int kt, waves_m, waves_n, wm, np, fmt;
   bool persist;
-  RbFn fn;
-  char name[64];
+  Instance<RbParams> inst;
   int C() const { return 32 * wm * waves_m; }
   int nwin() const { return 32 * (4 / wm) * waves_n; }
 };
 
 #define HFGRB_ENTRY(KT, WMS, WNS, WM, NP, FMT, PS) \
-  { KT, WMS, WNS, WM, NP, FMT, PS, resblock_bf16x3<KT, WMS, WNS, WM, NP, FMT, PS>, {0} }
+  { KT, WMS, WNS, WM, NP, FMT, PS, {resblock_bf16x3<KT, WMS, WNS, WM, NP, FMT, PS>, {0}} }
 #define HFGRB_KTS(WMS, WNS, WM, NP, FMT, PS)                                                 \
   HFGRB_ENTRY(3, WMS, WNS, WM, NP, FMT, PS), HFGRB_ENTRY(5, WMS, WNS, WM, NP, FMT, PS),      \
       HFGRB_ENTRY(7, WMS, WNS, WM, NP, FMT, PS), HFGRB_ENTRY(11, WMS, WNS, WM, NP, FMT, PS)
@@ -170,7 +166,7 @@ EntryRb g_entriesRb[] = {HFGRB_SET(3, 0), HFGRB_SET(3, 1), HFGRB_SET(2, 1)};
 
 // ResBlock2 (resblock2_bf16x3): the same shapes per C, one window per block
 #define HFGRB2_ENTRY(KT, WMS, WNS, WM, NP, FMT) \
-  { KT, WMS, WNS, WM, NP, FMT, false, resblock2_bf16x3<KT, WMS, WNS, WM, NP, FMT>, {0} }
+  { KT, WMS, WNS, WM, NP, FMT, false, {resblock2_bf16x3<KT, WMS, WNS, WM, NP, FMT>, {0}} }
 #define HFGRB2_KTS(WMS, WNS, WM, NP, FMT)                                       \
   HFGRB2_ENTRY(3, WMS, WNS, WM, NP, FMT), HFGRB2_ENTRY(5, WMS, WNS, WM, NP, FMT), \
       HFGRB2_ENTRY(7, WMS, WNS, WM, NP, FMT), HFGRB2_ENTRY(11, WMS, WNS, WM, NP, FMT)
@@ -204,6 +200,35 @@ size_t rb_lds_bytes(int C, int nwin, int n_conv) {
   return (size_t)C * rows * 4 + sizeof(float) * ((size_t)n_conv * C + 16);
 }
 
+namespace {
+// What both ResBlock launchers share once the instance is chosen: the window, halo and
+// dilation-margin checks, the LDS size, the grid and the launch.
+hipError_t launch_rb(EntryRb* e, const char* kernel, int C, int nwin, int kt, const RbParams& p,
+                     int batch, hipStream_t stream, const char** name) {
+  if (!e || p.n_conv > kRbMaxConv || batch < 1) return hipErrorInvalidValue;
+  if (p.W <= 0 || p.halo < 0 || p.W + 2 * p.halo > nwin) return hipErrorInvalidValue;
+  for (int i = 0; i < p.n_conv; ++i)
+    if (p.dil[i] < 1 || (kt - 1) / 2 * p.dil[i] > rb_marg(C, nwin)) return hipErrorInvalidValue;
+  size_t lds = rb_lds_bytes(C, nwin, p.n_conv);
+#if HFG_RB_TIMING
+  lds += kRbTsSlots * 8;  // + the stamps
+#endif
+  const int n_tiles = (p.L + p.W - 1) / p.W;
+  dim3 grid(n_tiles, batch);
+  if (p.persist) {
+    const int64_t n_win = (int64_t)n_tiles * batch;
+    if (n_win >= (1ll << 31)) return hipErrorInvalidValue;
+    grid = dim3((int)std::min<int64_t>(n_win, p.persist), 1);
+  }
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "%s<%d, %d, %d, %d, %d, %d%s>", kernel, e->kt, e->waves_m, e->waves_n, e->wm,
+             e->np, e->fmt, e->persist ? ", persist" : "");
+  };
+  return launch_instance(e->inst, fmt_name, grid, dim3(64 * e->waves_m * e->waves_n), lds, stream,
+                         name, p);
+}
+}  // namespace
+
 hipError_t launch_resblock_bf16x3(int C, int nwin, int wm, int kt, int fmt, int np,
                                   const RbParams& p_in, int batch, hipStream_t stream,
                                   const char** name) {
@@ -215,41 +240,14 @@ hipError_t launch_resblock_bf16x3(int C, int nwin, int wm, int kt, int fmt, int 
     p.persist = 0;
     e = find_rb(C, nwin, wm, kt, np, fmt);
   }
-  if (!e) return hipErrorInvalidValue;
-  if (p.n_conv < 2 || p.n_conv > kRbMaxConv || (p.n_conv & 1)) return hipErrorInvalidValue;
+  // conv pairs from conv0 of the packed stream; the fused conv_post on C = 32, one window per block
+  if (p.n_conv < 2 || (p.n_conv & 1)) return hipErrorInvalidValue;
   if (p.conv0 < 0 || p.conv0 + p.n_conv > p.n_conv_stream) return hipErrorInvalidValue;
-  if (p.W <= 0 || p.halo < 0 || p.W + 2 * p.halo > nwin) return hipErrorInvalidValue;
   if (p.wav && (C != 32 || wm != 1 || p.L % 4 || p.W % 4 || p.halo < 4 || !p.post_w || !p.post_b ||
                 p.amax_out || p.persist))
     return hipErrorInvalidValue;
-  if (p.persist < 0 || batch < 1) return hipErrorInvalidValue;
-  for (int i = 0; i < p.n_conv; ++i)
-    if (p.dil[i] < 1 || (kt - 1) / 2 * p.dil[i] > rb_marg(C, nwin)) return hipErrorInvalidValue;
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "resblock_bf16x3<%d, %d, %d, %d, %d, %d%s>", e->kt,
-               e->waves_m, e->waves_n, e->wm, e->np, e->fmt, e->persist ? ", persist" : "");
-  }
-#if HFG_RB_TIMING
-  const size_t lds = rb_lds_bytes(C, nwin, p.n_conv) + kRbTsSlots * 8;  // + the stamps
-#else
-  const size_t lds = rb_lds_bytes(C, nwin, p.n_conv);
-#endif
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  if (name) *name = e->name;
-  const int n_tiles = (p.L + p.W - 1) / p.W;
-  if (p.persist) {
-    const int64_t n_win = (int64_t)n_tiles * batch;
-    if (n_win >= (1ll << 31)) return hipErrorInvalidValue;
-    const int g = (int)std::min<int64_t>(n_win, p.persist);
-    e->fn<<<dim3(g, 1), dim3(64 * e->waves_m * e->waves_n), lds, stream>>>(p);
-  } else {
-    e->fn<<<dim3(n_tiles, batch), dim3(64 * e->waves_m * e->waves_n), lds, stream>>>(p);
-  }
-  return hipGetLastError();
+  if (p.persist < 0) return hipErrorInvalidValue;
+  return launch_rb(e, "resblock_bf16x3", C, nwin, kt, p, batch, stream, name);
 }
 
 bool rb2_supported(int C, int kt, int nwin, int wm) {
@@ -261,32 +259,11 @@ hipError_t launch_resblock2_bf16x3(int C, int nwin, int wm, int kt, int fmt, int
                                    const char** name) {
   RbParams p = p_in;
   p.batch = batch;
-  EntryRb* e = find_in(g_entriesRb2, C, nwin, wm, kt, np, fmt, false);
-  if (!e) return hipErrorInvalidValue;
-  if (p.n_conv < 1 || p.n_conv > kRbMaxConv || p.conv0 != 0 || p.n_conv_stream != p.n_conv)
-    return hipErrorInvalidValue;
-  if (p.W <= 0 || p.halo < 0 || p.W + 2 * p.halo > nwin) return hipErrorInvalidValue;
-  if (p.wav || p.persist || batch < 1) return hipErrorInvalidValue;
-  for (int i = 0; i < p.n_conv; ++i)
-    if (p.dil[i] < 1 || (kt - 1) / 2 * p.dil[i] > rb_marg(C, nwin)) return hipErrorInvalidValue;
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "resblock2_bf16x3<%d, %d, %d, %d, %d, %d>", e->kt,
-               e->waves_m, e->waves_n, e->wm, e->np, e->fmt);
-  }
-#if HFG_RB_TIMING
-  const size_t lds = rb_lds_bytes(C, nwin, p.n_conv) + kRbTsSlots * 8;  // + the stamps
-#else
-  const size_t lds = rb_lds_bytes(C, nwin, p.n_conv);
-#endif
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn)))
-    return err;
-  if (name) *name = e->name;
-  const int n_tiles = (p.L + p.W - 1) / p.W;
-  e->fn<<<dim3(n_tiles, batch), dim3(64 * e->waves_m * e->waves_n), lds, stream>>>(p);
-  return hipGetLastError();
+  // the whole stream (any count from 1), one window per block, no fused conv_post
+  if (p.n_conv < 1 || p.conv0 != 0 || p.n_conv_stream != p.n_conv) return hipErrorInvalidValue;
+  if (p.wav || p.persist) return hipErrorInvalidValue;
+  return launch_rb(find_in(g_entriesRb2, C, nwin, wm, kt, np, fmt, false), "resblock2_bf16x3", C,
+                   nwin, kt, p, batch, stream, name);
 }
 
 }  // namespace hfg

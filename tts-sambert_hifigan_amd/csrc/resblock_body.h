@@ -111,7 +111,7 @@ resblock_bf16x3(const RbParams p) {
   const int QT = p.n_conv_stream * STEPS;
   const int Q0 = p.conv0 * STEPS;
   const int dbg = p.dbg;
-  auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * half; };
+  auto rrow = [&](int r) { return acc_row(r, half); };
 
   for (int i = tid; i < n_conv * C; i += NT) bias_s[i] = p.bias[i];
 
@@ -150,7 +150,7 @@ resblock_bf16x3(const RbParams p) {
   // 4-GiB item would lose its last float), so every offset and its dword end fit 32 bits;
   // the range is never relied on otherwise (masked lanes read offset 0).
   unsigned Lb = (unsigned)p.L * 4u;
-  auto srow = [&](int i, int r) { return (unsigned)(row0 + 32 * i + (r & 3) + 8 * (r >> 2)) * Lb; };
+  auto srow = [&](int i, int r) { return (unsigned)(row0 + 32 * i + acc_row(r)) * Lb; };
   const unsigned lrow = 4u * (unsigned)half * (unsigned)p.L;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.x + (int64_t)b * p.bs), 0, (int)0xFFFFFFFFu, 0x00020000);
@@ -241,7 +241,7 @@ resblock_bf16x3(const RbParams p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         dst[q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                  rs, (int)vo, (int)(((e & 3) + 8 * (e >> 2)) * Lb), 0));
+                                                  rs, (int)vo, (int)(acc_row(e) * Lb), 0));
     }
   };
   auto mask_mg = [&]() {
@@ -267,7 +267,7 @@ resblock_bf16x3(const RbParams p) {
       for (int i = 0; i < WM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          xcur[i][k][r] = xl[xb + (32 * i + (r & 3) + 8 * (r >> 2)) * ROWS + 32 * k];
+          xcur[i][k][r] = xl[xb + (32 * i + acc_row(r)) * ROWS + 32 * k];
 #pragma unroll
     for (int q = 0; q < MG_T; ++q) {
       const int t = min(tid + q * NT, n_mg > 0 ? n_mg - 1 : 0);
@@ -275,7 +275,7 @@ resblock_bf16x3(const RbParams p) {
       const int cw = MARG + (m < R0 ? m - R0 : NWIN + m - R0);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        mg[q][e] = xl[(16 * gq + 4 * hh + (e & 3) + 8 * (e >> 2)) * ROWS + cw];
+        mg[q][e] = xl[(16 * gq + acc_row(e, hh)) * ROWS + cw];
     }
   };
   auto write_margins = [&](float sc) {
@@ -289,10 +289,10 @@ resblock_bf16x3(const RbParams p) {
         bf16x8 h, l;
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
-          floatx2 a;
+          floatx2_ a;
           a[0] = fmaxf(mg[q][e] * sc, mg[q][e] * (kLReluSlope * sc));
           a[1] = fmaxf(mg[q][e + 1] * sc, mg[q][e + 1] * (kLReluSlope * sc));
-          bf16x2 hh2, ll;
+          bf16x2_ hh2, ll;
           split2<FMT>(a, hh2, ll);
           h[e] = hh2[0];
           h[e + 1] = hh2[1];
@@ -332,11 +332,11 @@ resblock_bf16x3(const RbParams p) {
           bf16x8 h, l;
 #pragma unroll
           for (int e = 0; e < 8; e += 2) {
-            floatx2 a;
+            floatx2_ a;
             const float v0 = v[i][k][gg * 8 + e], v1 = v[i][k][gg * 8 + e + 1];
             a[0] = fmaxf(v0 * f1, v0 * f2);
             a[1] = fmaxf(v1 * f1, v1 * f2);
-            bf16x2 hh, ll;
+            bf16x2_ hh, ll;
             split2<FMT>(a, hh, ll);
             h[e] = hh[0];
             h[e + 1] = hh[1];
@@ -419,12 +419,8 @@ resblock_bf16x3(const RbParams p) {
 #pragma unroll
       for (int k = 0; k < WN; ++k)
 #pragma unroll
-        for (int i = 0; i < WM; ++i) {
-          if constexpr (NP == 3)  // the weights' lo plane (zero for bf16-valued weights: NP 2)
-            acc[i][k] = mfma32<FMT>(ra_l[cur][i], bh[cur][k], acc[i][k]);
-          acc[i][k] = mfma32<FMT>(ra_h[cur][i], bl[cur][k], acc[i][k]);
-          acc[i][k] = mfma32<FMT>(ra_h[cur][i], bh[cur][k], acc[i][k]);
-        }
+        for (int i = 0; i < WM; ++i)
+          mma3<NP, FMT>(ra_h[cur][i], ra_l[cur][i], bh[cur][k], bl[cur][k], acc[i][k]);
       load_a(cur, qb + s_ + 2);
       if (s_ + 1 < STEPS) {
 #pragma unroll

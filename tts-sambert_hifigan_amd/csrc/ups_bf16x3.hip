@@ -37,6 +37,7 @@
 
 #include "bf16x3_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 // u = 2 epilogue: 16-B stores through a DPP pair swap (1) or 8-B stores (0)
 #ifndef HFG_UPS_PAIR
@@ -50,8 +51,6 @@
 namespace hfg {
 
 namespace {
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 }  // namespace
 
 // occupancy: the small tile (2 x 32 x 32 accumulators per class) fits 168 VGPRs, 3 waves per
@@ -176,10 +175,10 @@ ups_bf16x3(const UpsParams p) {
       bf16x8 hv, lv;
 #pragma unroll
       for (int e = 0; e < 8; e += 2) {
-        floatx2 a;
+        floatx2_ a;
         a[0] = okt[j] ? fmaxf(xv[e][j] * sx, xv[e][j] * sx1) : 0.f;
         a[1] = okt[j] ? fmaxf(xv[e + 1][j] * sx, xv[e + 1][j] * sx1) : 0.f;
-        bf16x2 hh, ll;
+        bf16x2_ hh, ll;
         split2<FMT>(a, hh, ll);
         hv[e] = hh[0];
         hv[e + 1] = hh[1];
@@ -251,13 +250,7 @@ ups_bf16x3(const UpsParams p) {
 #pragma unroll
           for (int tp = 0; tp < 2; ++tp) {
             const int o = c + tp;  // class L: offsets -1, 0 (o = 0, 1); class R: 0, +1 (1, 2)
-            if constexpr (NP == 3)
-              acc[c][i][k] = mfma32<FMT>(a[c][tp][1][i], bh[o],
-                                                                    acc[c][i][k]);
-            acc[c][i][k] = mfma32<FMT>(a[c][tp][0][i], bl[o],
-                                                                  acc[c][i][k]);
-            acc[c][i][k] = mfma32<FMT>(a[c][tp][0][i], bh[o],
-                                                                  acc[c][i][k]);
+            mma3<NP, FMT>(a[c][tp][0][i], a[c][tp][1][i], bh[o], bl[o], acc[c][i][k]);
           }
     }
     prio_other();
@@ -291,7 +284,7 @@ ups_bf16x3(const UpsParams p) {
         const bool quad_ok = me + 1 < T_b;
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-          const int co0 = rb + (r & 3) + 8 * (r >> 2);
+          const int co0 = rb + acc_row(r);
           const float b0 = p.bias[co0], b1 = p.bias[co0 + 1];
           const float l0 = __builtin_fmaf(acc[0][i][k][r], sc, b0);
           const float r0 = __builtin_fmaf(acc[1][i][k][r], sc, b0);
@@ -314,13 +307,13 @@ ups_bf16x3(const UpsParams p) {
           } else {
             // last frame of an odd-length utterance (even lane, its odd partner past T_b):
             // both channels' pairs as 8-B stores
-            floatx2 a, c;
+            floatx2_ a, c;
             a[0] = l0;
             a[1] = r0;
             c[0] = l1;
             c[1] = r1;
-            if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2*>(yb + (int64_t)co0 * p.L_out + 2 * m) = a;
-            if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2*>(yb + (int64_t)(co0 + 1) * p.L_out + 2 * m) = c;
+            if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2_*>(yb + (int64_t)co0 * p.L_out + 2 * m) = a;
+            if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2_*>(yb + (int64_t)(co0 + 1) * p.L_out + 2 * m) = c;
             t2(l0, r0);
             t2(l1, r1);
           }
@@ -329,12 +322,12 @@ ups_bf16x3(const UpsParams p) {
         // rows = channels: (L, R) = samples 2m, 2m + 1
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int co = rb + (r & 3) + 8 * (r >> 2);
+          const int co = rb + acc_row(r);
           const float bv = p.bias[co];
-          floatx2 v;
+          floatx2_ v;
           v[0] = __builtin_fmaf(acc[0][i][k][r], sc, bv);
           v[1] = __builtin_fmaf(acc[1][i][k][r], sc, bv);
-          if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2*>(yb + (int64_t)co * p.L_out + 2 * m) = v;
+          if (!(kAblate && (p.dbg & 262144))) *reinterpret_cast<floatx2_*>(yb + (int64_t)co * p.L_out + 2 * m) = v;
           t2(v[0], v[1]);
         }
       } else if (h == 2) {
@@ -382,22 +375,18 @@ ups_bf16x3(const UpsParams p) {
 
 namespace {
 
-typedef void (*UpsFn)(const UpsParams);
-
 struct EntryUps {
   int cfg, np, fmt;
-  UpsFn fn;
-  char name[64];
+  Instance<UpsParams> inst;
 };
 
-#define HFGUPS_ENTRY(CFG, NP, FMT)                                                           \
-  {                                                                                          \
-    CFG, NP, FMT,                                                                            \
-        ups_bf16x3<kUpsCfgs[CFG].WAVES_M, kUpsCfgs[CFG].WAVES_N, kUpsCfgs[CFG].WM,          \
-                   kUpsCfgs[CFG].WN, NP, FMT>,                                               \
-    {                                                                                        \
-      0                                                                                      \
-    }                                                                                        \
+#define HFGUPS_ENTRY(CFG, NP, FMT)                                                    \
+  {                                                                                   \
+    CFG, NP, FMT, {                                                                   \
+      ups_bf16x3<kUpsCfgs[CFG].WAVES_M, kUpsCfgs[CFG].WAVES_N, kUpsCfgs[CFG].WM,      \
+                 kUpsCfgs[CFG].WN, NP, FMT>,                                          \
+          {0}                                                                         \
+    }                                                                                 \
   }
 
 // bf16x3 (NP 3, bf16), f16x3 (NP 3, f16), bf16w (NP 2 on the f16 kernel)
@@ -425,19 +414,12 @@ hipError_t launch_ups_bf16x3(int cfg, int fmt, int np, const UpsParams& p, hipSt
       !ups_rate_ok(p.u) || p.L_out < p.L * p.u || p.m_tiles * t.MT() * 2 != p.C_out * p.u ||
       p.n_tiles * t.NTILE() < p.T || (int64_t)p.C_in * p.L > ((int64_t)1 << 30))
     return hipErrorInvalidValue;
-  {
-    std::lock_guard<std::mutex> lk(setup_mutex());
-    if (!e->name[0])
-      snprintf(e->name, sizeof(e->name), "ups_bf16x3<%d, %d, %d, %d, %d, %d>", t.WAVES_M,
-               t.WAVES_N, t.WM, t.WN, np, fmt);
-  }
-  const size_t lds = ups_lds_bytes(cfg);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t err = ensure_max_lds(reinterpret_cast<const void*>(e->fn))) return err;
-  if (name) *name = e->name;
+  auto fmt_name = [&](char* s, size_t n) {
+    snprintf(s, n, "ups_bf16x3<%d, %d, %d, %d, %d, %d>", t.WAVES_M, t.WAVES_N, t.WM, t.WN, np, fmt);
+  };
   const int blocks = p.m_tiles * p.n_tiles * p.batch;
-  e->fn<<<dim3(blocks), dim3(t.threads()), lds, stream>>>(p);
-  return hipGetLastError();
+  return launch_instance(e->inst, fmt_name, dim3(blocks), dim3(t.threads()), ups_lds_bytes(cfg),
+                         stream, name, p);
 }
 
 }  // namespace hfg
