@@ -48,6 +48,11 @@ int hfg_debug_packed_resblock(hfg_handle* h, int stage, int j, float* out, size_
  * is too small. */
 int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen);
 
+/* Window columns of the thin whole-MRF kernel of a C-channel stage (mfma == 0: mrf_thin,
+ * mfma != 0: mrf_thin_mfma), which the plan does not list: a launch's centre is that window
+ * less twice the stage's largest thin_halo.  0 when there is no such kernel. */
+int hfg_debug_thin_window(int C, int mfma);
+
 /* A Generator forward (one stream) that also copies the stage outputs the
  * reference's forward passes through (models/hifigan.py:238-251) into
  * caller-owned device buffers: taps[0] <- conv_pre [B][C0][T], taps[1 + 2i] <-

@@ -28,7 +28,9 @@ def conv1d(x, w, b, pad, dil):
     lout = length + 2 * pad - dil * (k - 1)
     y = np.zeros((bsz, cout, lout), dtype=np.float64)
     for j in range(k):
-        y += np.einsum("oc,bct->bot", w[:, :, j], xp[:, :, j * dil: j * dil + lout])
+        wj = np.ascontiguousarray(w[:, :, j])
+        for i in range(bsz):  # 2-D products of contiguous operands: BLAS (einsum here is not)
+            y[i] += wj @ np.ascontiguousarray(xp[i, :, j * dil: j * dil + lout])
     return y + b[None, :, None]
 
 
@@ -39,7 +41,8 @@ def conv_transpose1d(x, w, b, stride, pad):
     full = (length - 1) * stride + k
     y = np.zeros((bsz, cout, full), dtype=np.float64)
     for j in range(k):
-        contrib = np.einsum("co,bct->bot", w[:, :, j], x)  # [B, Cout, L]
+        wj = np.ascontiguousarray(w[:, :, j].T)
+        contrib = np.stack([wj @ x[i] for i in range(bsz)])  # [B, Cout, L], BLAS
         y[:, :, j: j + (length - 1) * stride + 1: stride] += contrib
     lout = full - 2 * pad
     return y[:, :, pad: pad + lout] + b[None, :, None]

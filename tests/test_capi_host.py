@@ -17,6 +17,9 @@ from oracle import config as C
 
 # kTiles of csrc/kernels.h: (WM, WN, WAVES_M, WAVES_N)
 TILES = [(2, 2, 2, 2), (2, 2, 1, 4), (1, 4, 1, 4)]
+# conv_bf16x3.hip fragment orders: tile -> (WAVES_M, WM, taps per chunk)
+WAVES = {0: (2, 2, 4), 1: (1, 2, 2), 2: (1, 1, 4), 3: (2, 2, 2), 4: (2, 1, 4), 5: (2, 2, 2),
+         6: (4, 2, 2)}
 
 
 def header_symbols():
@@ -31,7 +34,7 @@ def header_symbols():
 def test_library_exports_every_header_symbol(pkg):
     lib = pkg.load_library()
     syms = header_symbols()
-    assert len(syms) == 45
+    assert len(syms) == 46
     for s in sorted(syms):
         assert hasattr(lib, s), f"missing export {s}"
     assert set(syms) == set(pkg._lib.SIGNATURES), "ctypes signatures out of sync with headers"
@@ -261,9 +264,6 @@ def test_split_packing(pkg, preset, precision):
     for k, v in sd.items():
         h.set_weight(k, torch.from_numpy(v))
     h.commit()
-    # tile -> (WAVES_M, WM, TPC)
-    WAVES = {0: (2, 2, 4), 1: (1, 2, 2), 2: (1, 1, 4), 3: (2, 2, 2), 4: (2, 1, 4), 5: (2, 2, 2),
-             6: (4, 2, 2)}
     n_checked = 0
     for mod in ["conv_pre", "mrfs.0.resblocks.2.convs1.1", "mrfs.1.resblocks.0.convs2.1",
                 "mrfs.2.resblocks.1.convs1.0", "mrfs.3.resblocks.2.convs2.1"]:

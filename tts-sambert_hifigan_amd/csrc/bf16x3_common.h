@@ -14,7 +14,11 @@
 //     tensor's (activations) or layer's (weights) largest magnitude; the scales are exact, the
 //     accumulator is multiplied by 2^-(e_x + e_w) after the main loop, and a value the scaling
 //     leaves below the f16 normal range (< 2^-17 of that largest magnitude) keeps an absolute
-//     error <= 2^-39 of it.  The f16 MFMAs run at the bf16 rate (MI355X_MICROARCH.md).
+//     error <= 2^-39 of it (in general <= 2^-25 * 2^-e, half the f16 subnormal quantum of the
+//     scaled domain).  That holds while e is not clamped (x3_exp), i.e. for a largest magnitude
+//     in [2^-45, 2^75): a smaller tensor is scaled by 2^60 only and may be stored as zeros
+//     (absolute error <= its magnitude, < 2^-45), a larger one overflows f16 — fp32 is the
+//     mode for such values.  The f16 MFMAs run at the bf16 rate (MI355X_MICROARCH.md).
 //   Activation scales come from the producing launch: its epilogue folds max|stored value| of
 //   each batch item into a per-(launch, item) slot (amax_commit); the consuming launch reads
 //   the slot of its input (per item: a batch item's result does not depend on the others).  A

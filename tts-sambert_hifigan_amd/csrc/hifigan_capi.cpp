@@ -633,6 +633,10 @@ int hfg_debug_packed_resblock(hfg_handle* h, int stage, int j, float* out, size_
   return HFG_OK;
 }
 
+int hfg_debug_thin_window(int C, int mfma) {
+  return mfma ? hfg::thin_mfma_window(C) : hfg::thin_window(C);
+}
+
 // JSON description of everything the launch code reads from the plan (layers, whole-ResBlock
 // and thin-stage launches, packed-buffer offsets) and the sha256 of the packed image: the
 // fingerprint the host suite pins (tests/test_plan_host.py).  Commits pending weights first.

@@ -4,7 +4,11 @@
 it into f16 halves hi + lo (22 significant bits); hi*hi + hi*lo + lo*hi are summed in fp32 on
 the f16 matrix cores (csrc/bf16x3_common.h).  Its products miss the exact ones by ~2^-21
 relative, below the fp32 rounding the reference itself makes, so it meets the bars of exact
-fp32 on every golden fixture — the x4 "loud" ones included — at the bf16x3 rate.
+fp32 on every golden fixture — the x4 "loud" ones included — at the bf16x3 rate.  A value the
+scaling leaves under the f16 normal range keeps an absolute error <= 2^-39 of its tensor's
+(weights: layer's) largest magnitude while the scale exponent is not clamped (+-60), i.e. for
+a largest magnitude in [2^-45, 2^75); a smaller tensor may be stored as zeros, a larger one
+overflows f16 (tests/test_dynamic_range_host.py, tests/test_gpu_dynamic_range.py).
 
 ``bf16x3`` splits into bf16 halves without scaling: ~16-bit-mantissa products (stage error
 <= 2.5e-5 relative at every scale, tests/test_gpu_stages.py).  That meets the north star's
@@ -33,6 +37,26 @@ MEASURED = {
     "bf16x3": {1.0: "<= 9e-8 (g1-g5, g7, g8)", 2.0: "1.3e-5 (g6)",
                4.0: "g9 0 (saturated); g10 0.084, 99.83% within 1e-4"},
     "fp32": {1.0: "<= 6e-8", 2.0: "1.4e-6 (g6)", 4.0: "g9 0; g10 2.0e-3 (reference fp32 vs fp64: 1.35e-3)"},
+    # f16x3, tests/test_gpu_dynamic_range.py (evidence lines of the MI355X run): one column of
+    # a standalone block's input times R; max|hip - ref64| / max(1, max|ref64|) over the quiet
+    # columns (further than the receptive-field radius from the spike) and the hot ones; worst
+    # of the three window positions and of the whole-block / layer-per-launch schedules.  No
+    # underflow allowance is granted at R <= 2^16 (bar: 4e-6); the allowance at 2^30 is
+    # 2 * 2^-39 * max|operand| * max_row sum|w| summed over the block's convs.
+    "dynamic_range": {
+        "resblock_bf16x3 (C = 128 / 64 / 32, k = 3 / 7 / 11)": {
+            "2^10": "quiet <= 1.7e-7, hot <= 1.1e-7", "2^16": "quiet <= 1.8e-7, hot <= 1.4e-7",
+            "2^30": "C = 64 k = 3: quiet 2.4e-3 absolute (1.1e-3 relative; layers 2.5e-3) against "
+                    "an allowance of 1.27e-1; hot 4.8e-8 (bf16x3, unscaled: quiet 1.8e-6); spike on "
+                    "a window's last column 2.4e-3 against 1.46e-1, on the next window's first "
+                    "halo column 2.7e-3 against 1.59e-1"},
+        "resblock2_bf16x3 (C = 64, k = 3 / 7)": {
+            "2^10": "quiet <= 2.4e-7, hot <= 1.3e-7", "2^16": "quiet <= 2.4e-7, hot <= 8.8e-8"},
+        "mrf_thin_mfma (C = 16)": {
+            "2^10": "quiet 1.1e-7, hot 8.9e-8", "2^16": "quiet 1.0e-7, hot 5.9e-8"},
+        "mrf_thin (C = 8, fp32 VALU)": {
+            "2^10": "quiet 8.8e-8, hot 4.4e-8", "2^16": "quiet 8.8e-8, hot 7.9e-8"},
+    },
 }
 
 
