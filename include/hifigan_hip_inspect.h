@@ -21,7 +21,11 @@ extern "C" {
 /* Copy the packed image of one layer (module prefix, e.g. "ups.0") into out:
  * w_len packed GEMM weights followed by b_len per-row biases.  info[10]
  * receives {kind (0 conv, 1 ups, 2 post), M, KT, tile, m_tiles, n_chunks,
- * w_len, b_len, CK, MT}.  With out == NULL only info is filled (no commit). */
+ * w_len, b_len, CK, MT}.  With out == NULL only info is filled (no commit).
+ * "<module>#small" selects the layer's second packing for the small-grid tile and
+ * "<module>#frames" the output-frame upsampler's (info: M = rows per class C_out * u / 2,
+ * KT = 2, tile = its configuration, n_chunks = channel groups, b_len = C_out); HFG_EINVAL
+ * where the plan has no such packing. */
 int hfg_debug_packed_layer(hfg_handle* h, const char* mod, float* out, size_t cap,
                            int64_t* info);
 

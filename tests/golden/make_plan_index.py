@@ -39,6 +39,17 @@ MRF_L = (1, 255, 256, 4096)
 # handles whose dump is stored verbatim (the others: its sha256)
 VERBATIM = ("gen/v1/f16x3", "gen/v2star/bf16x3")
 V1_KERNELS, V1_DILS = [3, 7, 11], [[1, 3, 5]] * 3
+# channel widths off the power-of-two grid (tests/width_cases.py): every configuration in
+# every precision, and the standalone MRF entry at four of its widths
+WIDTH_MRF = (24, 40, 100, 200)
+
+
+def _width_cases():
+    tests = os.path.dirname(HERE)
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import width_cases
+    return width_cases
 
 
 def cases():
@@ -60,6 +71,13 @@ def cases():
         out.append((f"mrf/C128/marg/{prec}", "mrf", (128, V1_KERNELS, [[1, 3, 6]] * 3, "1", prec)))
         # (k-1) * d = 130 > kBf16x3MaxHalo = 128: that layer runs the fp32 kernel
         out.append((f"mrf/C64/halo/{prec}", "mrf", (64, V1_KERNELS, [[1, 3, 13]] * 3, "1", prec)))
+    W = _width_cases()
+    for name in W.CONFIGS:
+        for prec in PRECISIONS:
+            out.append((f"gen/{name}/{prec}", "gen", (name, prec, None)))
+    for ch in WIDTH_MRF:
+        out.append((f"mrf/C{ch}/rb1/f16x3", "mrf",
+                    (ch, V1_KERNELS, [list(d) for d in W.MRF_DILATIONS], "1", "f16x3")))
     return out
 
 
@@ -69,7 +87,8 @@ def _gen_state(name):
     if name == "release_v3":
         from tts_sambert_hifigan_amd import synth as S
         return S.RELEASE_V3, S.random_state_dict(S.RELEASE_V3, seed=0)
-    return C.PRESETS[name], C.make_state_dict(C.PRESETS[name], seed=0)
+    cfg = C.PRESETS[name] if name in C.PRESETS else _width_cases().CONFIGS[name]
+    return cfg, C.make_state_dict(cfg, seed=0)
 
 
 def _mrf_state_dict(ch, kernels, dils, resblock, seed=0):

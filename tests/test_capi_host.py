@@ -114,28 +114,53 @@ def test_set_weight_errors_and_commit(pkg):
     assert rc == -22  # host-only handle: no forward
 
 
-def unpack_gemm(info, packed, cin):
-    """Invert the fragment order of conv_kernels.hip → Wt[row][ci][j]."""
+def config_layers(cfg):
+    """Every GEMM layer of a Generator config in the handle's order, conv_post excluded:
+    [(module, kind (0 conv, 1 ups), C_in, C_out, k, dilation, stride)]."""
+    c0 = cfg.upsample_initial_channel
+    out = [("conv_pre", 0, cfg.n_mels, c0, 7, 1, 1)]
+    for i, (u, k) in enumerate(zip(cfg.upsample_rates, cfg.upsample_kernel_sizes)):
+        out.append((f"ups.{i}", 1, c0 >> i, c0 >> (i + 1), k, 1, u))
+    for i in range(len(cfg.upsample_rates)):
+        ch = c0 >> (i + 1)
+        for j, (kr, dils) in enumerate(zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes)):
+            out += [(f"mrfs.{i}.resblocks.{j}.convs1.{m}", 0, ch, ch, kr, d, 1)
+                    for m, d in enumerate(dils)]
+            out += [(f"mrfs.{i}.resblocks.{j}.convs2.{m}", 0, ch, ch, kr, 1, 1)
+                    for m in range(len(dils))]
+    return out
+
+
+def _scatter(shape, values, rows, cis, taps):
+    """out[rows, cis, taps] = values (broadcast index arrays), with every element of `out`
+    written exactly once: the packed order is a bijection onto the padded GEMM operand."""
+    out = np.full(shape, np.nan)
+    rows, cis, taps = np.broadcast_arrays(rows, cis, taps)
+    assert rows.size == out.size and values.shape == rows.shape
+    out[rows, cis, taps] = values
+    assert not np.isnan(out).any(), "packed order does not cover the padded operand"
+    return out
+
+
+def unpack_gemm_padded(info, packed):
+    """Invert the fragment order of conv_kernels.hip → the whole padded operand
+    Wt[m_tiles * MT][n_chunks * CK][KT] (float64), padding rows and channels included."""
     WM, WN, WAVES_M, WAVES_N = TILES[info["tile"]]
-    CK = info["CK"]
+    CK, KT = info["CK"], info["KT"]
     MT = 32 * WM * WAVES_M
     assert MT == info["MT"]
     KK = CK // 2
-    KT = info["KT"]
     shape = (info["m_tiles"], info["n_chunks"], KT, KK, WAVES_M, 64, WM)
-    p = packed.reshape(shape)
-    Wt = np.zeros((info["m_tiles"] * MT, info["n_chunks"] * CK, KT), np.float32)
-    lane = np.arange(64)
-    for mt in range(shape[0]):
-        for c in range(shape[1]):
-            for j in range(KT):
-                for kk in range(KK):
-                    for wv in range(WAVES_M):
-                        for wm in range(WM):
-                            rows = mt * MT + wv * 32 * WM + wm * 32 + (lane & 31)
-                            cis = c * CK + 2 * kk + (lane >> 5)
-                            Wt[rows, cis, j] = p[mt, c, j, kk, wv, :, wm]
-    return Wt[: info["M"], :cin, :]
+    p = np.asarray(packed, np.float64).reshape(shape)
+    mt, c, j, kk, wv, lane, wm = np.ogrid[tuple(slice(0, n) for n in shape)]
+    return _scatter((shape[0] * MT, shape[1] * CK, KT), p,
+                    mt * MT + wv * 32 * WM + wm * 32 + (lane & 31),
+                    c * CK + 2 * kk + (lane >> 5), j)
+
+
+def unpack_gemm(info, packed, cin):
+    """Invert the fragment order of conv_kernels.hip → Wt[row][ci][j]."""
+    return unpack_gemm_padded(info, packed)[: info["M"], :cin, :].astype(np.float32)
 
 
 def emulate_conv(Wt, bias_rows, x, off, dil, N):
@@ -304,28 +329,30 @@ def test_split_packing(pkg, preset, precision):
     assert n_checked >= 2
 
 
-def unpack_bf16x3(info, packed, waves, precision="bf16x3"):
-    """Invert conv_bf16x3's fragment order → Wt[row][ci][tap] (hi + lo, float64)."""
+def unpack_bf16x3_planes(info, packed, waves, precision="bf16x3"):
+    """Invert conv_bf16x3's fragment order → (hi, lo), each the whole padded operand
+    [m_tiles * MT][n_g * 16][n_tg * TPC] (float64), padding rows, channels and taps included."""
     wm_, WM, TPC = waves
     MT = info["MT"]
+    assert MT == 32 * WM * wm_
     n_chunks, KT = info["n_chunks"], info["KT"]
     n_tg = -(-KT // TPC)
     n_g = n_chunks // n_tg
-    u = packed.view(np.uint16).reshape(info["m_tiles"], n_g, n_tg, TPC, 2, wm_, WM, 64, 8)
-    val = dec(u[:, :, :, :, 0], precision, info["ew"]) + dec(u[:, :, :, :, 1], precision, info["ew"])
-    Wt = np.zeros((info["m_tiles"] * MT, n_g * 16, n_tg * TPC))
-    lane = np.arange(64)
-    for mt in range(info["m_tiles"]):
-        for g in range(n_g):
-            for tg in range(n_tg):
-                for jj in range(TPC):
-                    for wv in range(wm_):
-                        for wm in range(WM):
-                            rows = mt * MT + wv * 32 * WM + wm * 32 + (lane & 31)
-                            for e in range(8):
-                                Wt[rows, g * 16 + 8 * (lane >> 5) + e, tg * TPC + jj] = \
-                                    val[mt, g, tg, jj, wv, wm, :, e]
-    return Wt[: info["M"], :, :KT]
+    assert n_g * n_tg == n_chunks
+    shape = (info["m_tiles"], n_g, n_tg, TPC, wm_, WM, 64, 8)
+    u = packed.view(np.uint16).reshape(shape[:4] + (2,) + shape[4:])
+    mt, g, tg, jj, wv, wm, lane, e = np.ogrid[tuple(slice(0, n) for n in shape)]
+    idx = (mt * MT + wv * 32 * WM + wm * 32 + (lane & 31), g * 16 + 8 * (lane >> 5) + e,
+           tg * TPC + jj)
+    full = (shape[0] * MT, n_g * 16, n_tg * TPC)
+    return tuple(_scatter(full, dec(u[:, :, :, :, plane], precision, info["ew"]), *idx)
+                 for plane in (0, 1))
+
+
+def unpack_bf16x3(info, packed, waves, precision="bf16x3"):
+    """Invert conv_bf16x3's fragment order → Wt[row][ci][tap] (hi + lo, float64)."""
+    hi, lo = unpack_bf16x3_planes(info, packed, waves, precision)
+    return (hi + lo)[: info["M"], :, :info["KT"]]
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "f16x3"])

@@ -429,7 +429,8 @@ class Handle:
         return json.loads(buf.value.decode())
 
     def packed_layer(self, mod: str):
-        """(info dict, packed weights np.ndarray, per-row bias np.ndarray) of one layer."""
+        """(info dict, packed weights np.ndarray, per-row bias np.ndarray) of one layer;
+        ``"<module>#small"`` / ``"<module>#frames"``: its small-tile / output-frame packing."""
         import numpy as np
         info = (c_int64 * 10)()
         check(self.lib.hfg_debug_packed_layer(self.ptr, mod.encode(), None, 0, info))
@@ -438,7 +439,8 @@ class Handle:
         check(self.lib.hfg_debug_packed_layer(
             self.ptr, mod.encode(), out.ctypes.data_as(POINTER(c_float)), out.size, info))
         ew = c_int(0)
-        check(self.lib.hfg_debug_layer_exponent(self.ptr, mod.encode(), ctypes.byref(ew)))
+        check(self.lib.hfg_debug_layer_exponent(self.ptr, mod.split("#")[0].encode(),
+                                                ctypes.byref(ew)))
         keys = ["kind", "M", "KT", "tile", "m_tiles", "n_chunks", "w_len", "b_len", "CK", "MT"]
         d = dict(zip(keys, [int(v) for v in info]))
         d["ew"] = int(ew.value)

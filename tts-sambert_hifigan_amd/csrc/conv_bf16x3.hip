@@ -231,9 +231,14 @@ conv1d_bf16x3(const ConvParams p) {
           xv[q][e] = __builtin_bit_cast(
               float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)o0, e * xcs * 4, 0));
       } else {
+        // a half-row that starts at or past C_in (C_in % 16 in 1..8: ecap < 0, all eight
+        // elements masked) forms its addresses from channel C_in - 1 like the elements past
+        // ecap, never from channel cb: that one lies outside the item (conv_pre: outside the
+        // caller's mel on the last item)
+        const unsigned oc = tok ? (unsigned)(min(cb, p.C_in - 1) * xcs + gi * xts) * 4u : 0u;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const unsigned oe = o0 + (unsigned)max(min(e, ecap), 0) * step;
+          const unsigned oe = oc + (unsigned)max(min(e, ecap), 0) * step;
           xv[q][e] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(xb) + oe);
         }
       }

@@ -3,6 +3,7 @@
 // keyed by the reference state_dict names with weight-norm folding, the error channel and the
 // schedule-knob table.  The plan, the packers and the launch schedule are plan.cpp, pack.cpp
 // and forward.cpp (handle.h).
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -559,9 +560,42 @@ int hfg_profile_summary(hfg_handle* h, char* buf, size_t buflen) {
 int hfg_debug_packed_layer(hfg_handle* h, const char* mod, float* out, size_t cap,
                            int64_t* info) {
   if (!h || !mod) return fail(HFG_EINVAL, "NULL argument");
+  // "<module>#small": the layer's small-grid-tile packing; "<module>#frames": the output-frame
+  // upsampler's (ups_bf16x3) — HFG_EINVAL where the plan has none
+  std::string name(mod);
+  int which = 0;
+  const size_t hash = name.find('#');
+  if (hash != std::string::npos) {
+    const std::string sel = name.substr(hash + 1);
+    which = sel == "small" ? 1 : sel == "frames" ? 2 : -1;
+    if (which < 0) return fail(HFG_EINVAL, "unknown packing '%s' (small, frames)", sel.c_str());
+    name.resize(hash);
+  }
   for (auto& L : h->layers) {
-    if (L.mod != mod) continue;
-    const Packing& pk = L.pk[0];
+    if (L.mod != name) continue;
+    if (which == 2) {
+      if (L.ups_cfg < 0) return fail(HFG_EINVAL, "%s has no output-frame packing", name.c_str());
+      const hfg::UpsCfg& tf = hfg::kUpsCfgs[L.ups_cfg];
+      const size_t w_len = (size_t)L.m_tiles_f * (L.C_in / 16) * 8 * tf.MT() * 16 / 2;
+      const size_t b_len = (size_t)L.C_out;
+      if (info) {
+        const int64_t v[10] = {L.kind, (int64_t)L.C_out * L.s / 2, 2, L.ups_cfg, L.m_tiles_f,
+                               L.C_in / 16, (int64_t)w_len, (int64_t)b_len, 16, tf.MT()};
+        std::copy_n(v, 10, info);
+      }
+      if (!out) return HFG_OK;
+      if (h->dirty) {
+        int rc = do_commit(h);
+        if (rc) return rc;
+      }
+      if (cap < w_len + b_len) return fail(HFG_EINVAL, "output buffer too small");
+      memcpy(out, h->packed_host.data() + L.wf_off, sizeof(float) * w_len);
+      memcpy(out + w_len, h->packed_host.data() + L.bf_off, sizeof(float) * b_len);
+      return HFG_OK;
+    }
+    const Packing& pk = L.pk[which];
+    if (which == 1 && pk.tile < 0)
+      return fail(HFG_EINVAL, "%s has no small-tile packing", name.c_str());
     if (info) {
       info[0] = L.kind;
       info[1] = L.M;
