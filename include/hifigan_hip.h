@@ -308,4 +308,12 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
 #ifdef __cplusplus
 }
 #endif
+
+/* ---------------------------------------------------------------------------
+ * The public HiFi-GAN release's mel front end (meldataset.mel_spectrogram:
+ * center=False framing, magnitude spectrum, librosa filterbank, clipped natural
+ * log) with per-item lengths: the hfg_relmel section, in a header of its own.
+ * ------------------------------------------------------------------------- */
+#include "hifigan_hip_relmel.h"
+
 #endif /* HIFIGAN_HIP_H */

@@ -224,6 +224,25 @@ SIGNATURES = {
 }
 
 
+class HfgRelmelConfig(ctypes.Structure):
+    """hfg_relmel_config: the release's config.json keys; 0 in fmax / spec_eps / clip_val
+    selects sampling_rate / 2, 1e-9 and 1e-5."""
+    _fields_ = [("sampling_rate", c_int32), ("n_fft", c_int32), ("hop_size", c_int32),
+                ("win_size", c_int32), ("num_mels", c_int32), ("fmin", c_float),
+                ("fmax", c_float), ("spec_eps", c_float), ("clip_val", c_float)]
+
+
+# every symbol declared in include/hifigan_hip_relmel.h (the release's mel front end)
+RELMEL_SIGNATURES = {
+    "hfg_relmel_create": (c_int, [POINTER(HfgRelmelConfig), c_int, POINTER(c_void_p)]),
+    "hfg_relmel_destroy": (None, [c_void_p]),
+    "hfg_relmel_set_tables": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float)]),
+    "hfg_relmel_frames": (c_int64, [c_void_p, c_int64]),
+    "hfg_relmel_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+}
+
+
 def load_library(path: str = LIB_PATH):
     """Open libhifigan_hip.so (cached).  Raises HipExtensionMissing if absent."""
     global _lib
@@ -238,7 +257,7 @@ def load_library(path: str = LIB_PATH):
     # opts in for a same-box A/B against a previous commit's build (HFG_ALLOW_OLD_LIB=1)
     allow_old = os.environ.get("HFG_ALLOW_OLD_LIB") == "1"
     missing = []
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             missing.append(name)

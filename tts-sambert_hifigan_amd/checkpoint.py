@@ -123,6 +123,20 @@ def generator_from_release_config(h: Mapping, precision: Optional[str] = None):
         precision=precision, resblock=str(h["resblock"]), final_lrelu_slope=0.01)
 
 
+def mel_from_release_config(h: Mapping, device=None):
+    """The release's mel front end (``meldataset.mel_spectrogram``) for its ``config.json``
+    (as a mapping): keys ``sampling_rate``, ``n_fft``, ``hop_size``, ``win_size``,
+    ``num_mels``, ``fmin`` and ``fmax`` (``null`` / None: ``sampling_rate / 2``).  The
+    counterpart of ``generator_from_release_config``: its mels are what the release's
+    checkpoints were trained on (``mel.ReleaseMelSpectrogram``)."""
+    from .mel import ReleaseMelSpectrogram
+    fmax = h.get("fmax")
+    return ReleaseMelSpectrogram(
+        sampling_rate=int(h["sampling_rate"]), n_fft=int(h["n_fft"]),
+        hop_size=int(h["hop_size"]), win_size=int(h["win_size"]), num_mels=int(h["num_mels"]),
+        fmin=float(h["fmin"]), fmax=None if fmax is None else float(fmax), device=device)
+
+
 def load_generator_checkpoint(gen, src: Union[str, Mapping], strict: bool = True,
                               map_location: Optional[str] = "cpu"):
     """Load a checkpoint file (``torch.load(..., weights_only=True)``) or mapping into

@@ -76,6 +76,81 @@ struct hfg_mel_handle {
 
 namespace {
 
+// Host side of the FFT kernels' tables (logmel_fft, release_mel_fft): e^{-2 pi i t / N} in
+// float64 and, from a filterbank [n_bins][n_mels], each band's (first bin, end bin, offset)
+// and its nonzero weights.
+struct FftTables {
+  std::vector<double> tw;
+  std::vector<int> band;
+  std::vector<float> bw;
+};
+FftTables fft_host_tables(int N, int n_bins, int n_mels, const float* fb) {
+  const double two_pi = 6.283185307179586476925286766559;
+  FftTables t;
+  t.tw.resize(2 * (size_t)N);
+  for (int i = 0; i < N; ++i) {
+    t.tw[2 * i] = std::cos(two_pi * i / N);
+    t.tw[2 * i + 1] = -std::sin(two_pi * i / N);
+  }
+  t.band.resize(3 * (size_t)n_mels);
+  for (int m = 0; m < n_mels; ++m) {
+    int lo = n_bins, hi = 0;
+    for (int k = 0; k < n_bins; ++k)
+      if (fb[(size_t)k * n_mels + m] != 0.f) {
+        lo = std::min(lo, k);
+        hi = k + 1;
+      }
+    if (hi <= lo) lo = hi = 0;
+    t.band[3 * m] = lo;
+    t.band[3 * m + 1] = hi;
+    t.band[3 * m + 2] = (int)t.bw.size();
+    for (int k = lo; k < hi; ++k) t.bw.push_back(fb[(size_t)k * n_mels + m]);
+  }
+  if (t.bw.empty()) t.bw.push_back(0.f);
+  return t;
+}
+
+struct Tbl {
+  void** dst;
+  const void* src;
+  size_t bytes;
+  void* fresh;
+};
+// Upload every table of `tbls` to `device` and swap it into its handle slot.  Every new
+// table is allocated and filled before any old one is released: a failure leaves the
+// handle's previous (complete) tables in place.  A forward still in flight may
+// read an old table, so those go to `retired` (freed at destroy).
+int swap_tables(int device, std::vector<Tbl>& tbls, std::vector<void*>& retired) {
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return mfail(HFG_ENODEV, "hipSetDevice(%d)", device);
+  bool ok = true;
+  for (auto& t : tbls) {
+    ok = hipMalloc(&t.fresh, t.bytes) == hipSuccess &&
+         hipMemcpy(t.fresh, t.src, t.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) break;
+  }
+  constexpr size_t kMaxRetired = 256;
+  if (ok && retired.size() + tbls.size() > kMaxRetired) {
+    // rare (hundreds of replacements): one sync retires every old table at once
+    ok = hipDeviceSynchronize() == hipSuccess;
+    if (ok) {
+      for (void* p : retired) (void)hipFree(p);
+      retired.clear();
+    }
+  }
+  for (auto& t : tbls) {
+    if (ok) {
+      if (*t.dst) retired.push_back(*t.dst);
+      *t.dst = t.fresh;
+    } else if (t.fresh) {
+      (void)hipFree(t.fresh);
+    }
+  }
+  if (prev >= 0) (void)hipSetDevice(prev);
+  return ok ? HFG_OK : mfail(HFG_ENOMEM, "mel tables: device allocation / copy failed");
+}
+
 // Build and upload every device table from a window [n_fft] and a filterbank
 // [n_bins][n_mels] (host, fp32): the DFT-GEMM path's windowed twiddles, the FFT path's
 // window, e^{-2 pi i t / N} (float64) and each band's nonzero bins.
@@ -95,39 +170,8 @@ int upload_tables(hfg_mel_handle* h, const float* win, const float* fb) {
         ts[(size_t)n * h->bins_pad + k] = (float)(-(double)win[n] * std::sin(ang));
       }
   }
-  std::vector<double> tw_h(2 * (size_t)N);
-  for (int t = 0; t < N; ++t) {
-    tw_h[2 * t] = std::cos(two_pi * t / N);
-    tw_h[2 * t + 1] = -std::sin(two_pi * t / N);
-  }
-  std::vector<int> band_h(3 * (size_t)n_mels);
-  std::vector<float> bw_h;
-  for (int m = 0; m < n_mels; ++m) {
-    int lo = h->n_bins, hi = 0;
-    for (int k = 0; k < h->n_bins; ++k)
-      if (fb[(size_t)k * n_mels + m] != 0.f) {
-        lo = std::min(lo, k);
-        hi = k + 1;
-      }
-    if (hi <= lo) lo = hi = 0;
-    band_h[3 * m] = lo;
-    band_h[3 * m + 1] = hi;
-    band_h[3 * m + 2] = (int)bw_h.size();
-    for (int k = lo; k < hi; ++k) bw_h.push_back(fb[(size_t)k * n_mels + m]);
-  }
-  if (bw_h.empty()) bw_h.push_back(0.f);
+  const FftTables ft = fft_host_tables(N, h->n_bins, n_mels, fb);
   if (h->device < 0) return HFG_OK;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(HFG_ENODEV, "hipSetDevice(%d)", h->device);
-  // every new table is allocated and filled before any old one is released: a failure leaves
-  // the handle's previous (complete) tables in place
-  struct Tbl {
-    void** dst;
-    const void* src;
-    size_t bytes;
-    void* fresh;
-  };
   std::vector<Tbl> tbls;
   if (!h->fft) {
     tbls.push_back({reinterpret_cast<void**>(&h->tcos), tc.data(), tc.size() * 4, nullptr});
@@ -135,35 +179,10 @@ int upload_tables(hfg_mel_handle* h, const float* win, const float* fb) {
     tbls.push_back({reinterpret_cast<void**>(&h->fb), fb, h->fb_host.size() * 4, nullptr});
   }
   tbls.push_back({reinterpret_cast<void**>(&h->win), win, (size_t)N * 4, nullptr});
-  tbls.push_back({&h->tw, tw_h.data(), tw_h.size() * 8, nullptr});
-  tbls.push_back({reinterpret_cast<void**>(&h->band), band_h.data(), band_h.size() * 4, nullptr});
-  tbls.push_back({reinterpret_cast<void**>(&h->bw), bw_h.data(), bw_h.size() * 4, nullptr});
-  bool ok = true;
-  for (auto& t : tbls) {
-    ok = hipMalloc(&t.fresh, t.bytes) == hipSuccess &&
-         hipMemcpy(t.fresh, t.src, t.bytes, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) break;
-  }
-  constexpr size_t kMaxRetired = 256;
-  if (ok && h->retired.size() + tbls.size() > kMaxRetired) {
-    // rare (hundreds of replacements): one sync retires every old table at once
-    ok = hipDeviceSynchronize() == hipSuccess;
-    if (ok) {
-      for (void* p : h->retired) (void)hipFree(p);
-      h->retired.clear();
-    }
-  }
-  for (auto& t : tbls) {
-    if (ok) {
-      // a forward in flight may still read the old table: retired, freed at destroy
-      if (*t.dst) h->retired.push_back(*t.dst);
-      *t.dst = t.fresh;
-    } else if (t.fresh) {
-      (void)hipFree(t.fresh);
-    }
-  }
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return ok ? HFG_OK : mfail(HFG_ENOMEM, "mel tables: device allocation / copy failed");
+  tbls.push_back({&h->tw, ft.tw.data(), ft.tw.size() * 8, nullptr});
+  tbls.push_back({reinterpret_cast<void**>(&h->band), ft.band.data(), ft.band.size() * 4, nullptr});
+  tbls.push_back({reinterpret_cast<void**>(&h->bw), ft.bw.data(), ft.bw.size() * 4, nullptr});
+  return swap_tables(h->device, tbls, h->retired);
 }
 
 }  // namespace
@@ -444,6 +463,156 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
     e = hfg::launch_resample(x, B, n, n_out, h->kern, h->new_, h->orig, h->klen, h->width, y, s);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   if (e != hipSuccess) return mfail(HFG_EIO, "resample launch: %s", hipGetErrorString(e));
+  return HFG_OK;
+}
+
+}  // extern "C"
+
+// ---- the public HiFi-GAN release's mel front end (include/hifigan_hip_relmel.h) ---------
+// meldataset.mel_spectrogram: reflect pad (n_fft - hop) / 2, torch.stft(center=False),
+// sqrt(re^2 + im^2 + 1e-9), librosa.filters.mel, ln(max(mel, 1e-5)); one launch of
+// release_mel_fft (release_mel.hip), per-item lengths.
+struct hfg_relmel_handle {
+  hfg_relmel_config cfg;  // with fmax, spec_eps and clip_val resolved
+  int device;
+  int n_bins;
+  int fpw;
+  float* win = nullptr;   // [n_fft] fp32
+  void* tw = nullptr;     // [n_fft] complex double
+  int* band = nullptr;    // [num_mels] x (first bin, end bin, offset into bw)
+  float* bw = nullptr;    // the bands' nonzero weights
+  std::vector<void*> retired;  // replaced tables (a forward in flight may read them)
+};
+
+namespace {
+
+// librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) (htk=False, norm="slaney") in double:
+// out[k][m], k < n_fft/2 + 1 (librosa's Slaney hz_to_mel / mel_to_hz are torchaudio's).
+void librosa_mel(const hfg_relmel_config* c, float* out) {
+  const int n_bins = c->n_fft / 2 + 1, n_mels = c->num_mels;
+  std::vector<double> fftfreqs(n_bins), mel_f(n_mels + 2);
+  const double fstep = (0.5 * c->sampling_rate) / (double)(n_bins - 1);
+  for (int k = 0; k < n_bins; ++k) fftfreqs[k] = k * fstep;
+  fftfreqs[n_bins - 1] = 0.5 * c->sampling_rate;
+  const double m_min = hz_to_mel(c->fmin, 1), m_max = hz_to_mel(c->fmax, 1);
+  const double mstep = (m_max - m_min) / (double)(n_mels + 1);
+  for (int i = 0; i < n_mels + 2; ++i)
+    mel_f[i] = mel_to_hz(i == n_mels + 1 ? m_max : m_min + i * mstep, 1);
+  for (int m = 0; m < n_mels; ++m) {
+    const double enorm = 2.0 / (mel_f[m + 2] - mel_f[m]);
+    for (int k = 0; k < n_bins; ++k) {
+      const double lower = -(mel_f[m] - fftfreqs[k]) / (mel_f[m + 1] - mel_f[m]);
+      const double upper = (mel_f[m + 2] - fftfreqs[k]) / (mel_f[m + 2] - mel_f[m + 1]);
+      out[(size_t)k * n_mels + m] = (float)(std::fmax(0.0, std::fmin(lower, upper)) * enorm);
+    }
+  }
+}
+
+int relmel_upload(hfg_relmel_handle* h, const float* win, const float* fb) {
+  const FftTables ft = fft_host_tables(h->cfg.n_fft, h->n_bins, h->cfg.num_mels, fb);
+  if (h->device < 0) return HFG_OK;
+  std::vector<Tbl> tbls;
+  tbls.push_back({reinterpret_cast<void**>(&h->win), win, (size_t)h->cfg.n_fft * 4, nullptr});
+  tbls.push_back({&h->tw, ft.tw.data(), ft.tw.size() * 8, nullptr});
+  tbls.push_back({reinterpret_cast<void**>(&h->band), ft.band.data(), ft.band.size() * 4, nullptr});
+  tbls.push_back({reinterpret_cast<void**>(&h->bw), ft.bw.data(), ft.bw.size() * 4, nullptr});
+  return swap_tables(h->device, tbls, h->retired);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hfg_relmel_create(const hfg_relmel_config* cfg, int device, hfg_relmel_handle** out) {
+  if (!cfg || !out) return mfail(HFG_EINVAL, "NULL argument");
+  *out = nullptr;
+  hfg_relmel_config c = *cfg;
+  if (c.sampling_rate <= 0 || c.n_fft <= 0 || c.hop_size <= 0 || c.win_size <= 0 ||
+      c.num_mels <= 0)
+    return mfail(HFG_EINVAL, "invalid release mel configuration");
+  if (c.n_fft < 16 || (c.n_fft & (c.n_fft - 1)))
+    return mfail(HFG_EINVAL, "release mel: n_fft must be a power of two >= 16, got %d", c.n_fft);
+  if (c.hop_size > c.n_fft || ((c.n_fft - c.hop_size) & 1))
+    return mfail(HFG_EINVAL, "release mel: n_fft - hop_size must be even and >= 0 (n_fft %d, "
+                 "hop_size %d)", c.n_fft, c.hop_size);
+  if (c.win_size > c.n_fft) return mfail(HFG_EINVAL, "release mel: win_size > n_fft");
+  if (!(c.fmax > 0.f)) c.fmax = 0.5f * (float)c.sampling_rate;  // the release's null
+  if (!(c.fmin >= 0.f) || !(c.fmax > c.fmin))
+    return mfail(HFG_EINVAL, "release mel: need 0 <= fmin < fmax");
+  if (c.spec_eps == 0.f) c.spec_eps = 1e-9f;
+  if (c.clip_val == 0.f) c.clip_val = 1e-5f;
+  if (!(c.spec_eps > 0.f) || !(c.clip_val > 0.f))
+    return mfail(HFG_EINVAL, "release mel: spec_eps and clip_val must be > 0");
+  const int fpw = c.n_fft <= 1024 ? 2 : 1;
+  if (hfg::logmel_fft_lds_bytes(c.n_fft, c.hop_size, fpw, c.num_mels) > hfg::kMaxLdsBytes)
+    return mfail(HFG_EINVAL, "release mel: n_fft %d / num_mels %d too large for the LDS frame "
+                 "tile", c.n_fft, c.num_mels);
+  auto* h = new (std::nothrow) hfg_relmel_handle();
+  if (!h) return mfail(HFG_ENOMEM, "host alloc");
+  h->cfg = c;
+  h->device = device;
+  h->n_bins = c.n_fft / 2 + 1;
+  h->fpw = fpw;
+  const int N = c.n_fft, W = c.win_size, left = (N - W) / 2;
+  const double two_pi = 6.283185307179586476925286766559;
+  std::vector<float> win_h(N, 0.f);
+  for (int n = 0; n < N; ++n) {
+    const int wi = n - left;
+    win_h[n] = (wi >= 0 && wi < W) ? (float)(0.5 - 0.5 * std::cos(two_pi * wi / W)) : 0.f;
+  }
+  std::vector<float> fb_h((size_t)h->n_bins * c.num_mels);
+  librosa_mel(&c, fb_h.data());
+  int rc = relmel_upload(h, win_h.data(), fb_h.data());
+  if (rc) {
+    hfg_relmel_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return HFG_OK;
+}
+
+void hfg_relmel_destroy(hfg_relmel_handle* h) {
+  if (!h) return;
+  if (h->win) (void)hipFree(h->win);
+  if (h->tw) (void)hipFree(h->tw);
+  if (h->band) (void)hipFree(h->band);
+  if (h->bw) (void)hipFree(h->bw);
+  for (void* p : h->retired) (void)hipFree(p);
+  delete h;
+}
+
+int hfg_relmel_set_tables(hfg_relmel_handle* h, const float* window, const float* fb) {
+  if (!h || !window || !fb) return mfail(HFG_EINVAL, "NULL argument");
+  return relmel_upload(h, window, fb);
+}
+
+int64_t hfg_relmel_frames(const hfg_relmel_handle* h, int64_t n_samples) {
+  if (!h) return -1;
+  const int64_t pad = (h->cfg.n_fft - h->cfg.hop_size) / 2;
+  if (n_samples <= pad || n_samples < h->cfg.hop_size) return -1;
+  return n_samples / h->cfg.hop_size;
+}
+
+int hfg_relmel_forward(hfg_relmel_handle* h, const float* wav, int64_t B, int64_t n_samples,
+                       const int32_t* lengths, float* mel, int32_t* frame_lengths, void* stream) {
+  if (!h || !wav || !mel) return mfail(HFG_EINVAL, "NULL argument");
+  if (h->device < 0) return mfail(HFG_EINVAL, "host-only release mel handle");
+  if (B <= 0 || B > 65535) return mfail(HFG_EINVAL, "B must be in [1, 65535]");
+  const int64_t n_frames = hfg_relmel_frames(h, n_samples);
+  if (n_frames < 1 || n_frames > INT32_MAX)
+    return mfail(HFG_EINVAL, "release mel: %lld samples give no frame (need more than "
+                 "(n_fft - hop) / 2 = %d and at least hop = %d)", (long long)n_samples,
+                 (h->cfg.n_fft - h->cfg.hop_size) / 2, h->cfg.hop_size);
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (prev != h->device && hipSetDevice(h->device) != hipSuccess)
+    return mfail(HFG_ENODEV, "hipSetDevice(%d)", h->device);
+  hipError_t e = hfg::launch_release_mel_fft(
+      wav, B, n_samples, lengths, h->cfg.n_fft, h->cfg.hop_size, h->fpw, h->win, h->tw, h->band,
+      h->bw, h->cfg.num_mels, h->cfg.spec_eps, h->cfg.clip_val, mel, frame_lengths,
+      reinterpret_cast<hipStream_t>(stream));
+  if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
+  if (e != hipSuccess) return mfail(HFG_EIO, "release mel launch: %s", hipGetErrorString(e));
   return HFG_OK;
 }
 

@@ -28,6 +28,19 @@ hipError_t launch_logmel_fft(const float* wav, int64_t B, int64_t n_samp, int n_
                              const int* band, const float* bw, int n_mels, float eps,
                              int log_mode, float ln_base, float* mel, hipStream_t stream);
 
+// The public HiFi-GAN release's mel (release_mel.hip), same tables and block shape as
+// launch_logmel_fft (and its LDS formula): mel[b][m][f] = ln(max(sum_{k in band m} bw[k]
+// sqrt(|X_f[k]|^2 + spec_eps), clip)), frame f = samples [f hop - p, f hop - p + n_fft),
+// p = (n_fft - hop) / 2 (even difference), reflected at 0 and at the item's length; mel rows
+// hold n_samp / hop columns.  lens (device int32 [B], or null = n_samp) is clamped into
+// [0, n_samp]; item b has len / hop frames when len > p and len >= hop, else 0; columns past
+// them get ln(clip); frame_lens (device int32 [B], or null) receives the frame counts.
+hipError_t launch_release_mel_fft(const float* wav, int64_t B, int64_t n_samp,
+                                  const int32_t* lens, int n_fft, int hop, int fpw,
+                                  const float* window, const void* tw, const int* band,
+                                  const float* bw, int n_mels, float spec_eps, float clip,
+                                  float* mel, int32_t* frame_lens, hipStream_t stream);
+
 // y[b][m] = sum_k x_pad[b][(m / n_phases) * stride + k] * kern[m % n_phases][k], m < n_out,
 // x_pad = x zero-padded by `width` on the left (torchaudio _apply_sinc_resample_kernel)
 hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,

@@ -16,6 +16,7 @@
 #include <cstdio>
 
 #include "epilogue.h"
+#include "fft_f64.h"
 #include "kernels.h"
 #include "launch.h"
 #include "mel_kernels.h"
@@ -118,81 +119,8 @@ mel_log(const float* __restrict__ power, int n_frames, int n_bins, const float* 
 // O(N^2) DFT GEMM (stft_power_mfma, kept for n_fft that are not a power of two).
 // Block: 4 waves x fpw frames; the block's reflect-padded sample span is staged once in
 // LDS (fp32) and the [n_mels][frames] tile leaves through LDS as frame-contiguous rows.
-struct cd {
-  double x, y;
-};
-__device__ __forceinline__ cd cmul(cd a, cd b) {
-  return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-__device__ __forceinline__ cd cadd(cd a, cd b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cd csub(cd a, cd b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ cd cmul_mi(cd a) { return {a.y, -a.x}; }  // (-i) a
-
-// in-register DFT of R points: out[q] = sum_r v[r] e^{-2 pi i r q / R}
-template <int R>
-__device__ __forceinline__ void dft_r(cd (&v)[R]);
-template <>
-__device__ __forceinline__ void dft_r<2>(cd (&v)[2]) {
-  const cd a = cadd(v[0], v[1]), b = csub(v[0], v[1]);
-  v[0] = a;
-  v[1] = b;
-}
-template <>
-__device__ __forceinline__ void dft_r<4>(cd (&v)[4]) {
-  const cd t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]);
-  const cd t2 = cadd(v[1], v[3]), t3 = cmul_mi(csub(v[1], v[3]));
-  v[0] = cadd(t0, t2);
-  v[2] = csub(t0, t2);
-  v[1] = cadd(t1, t3);
-  v[3] = csub(t1, t3);
-}
-template <>
-__device__ __forceinline__ void dft_r<8>(cd (&v)[8]) {
-  cd e[4] = {v[0], v[2], v[4], v[6]}, o[4] = {v[1], v[3], v[5], v[7]};
-  dft_r<4>(e);
-  dft_r<4>(o);
-  constexpr double s = 0.70710678118654752440;
-  o[1] = {s * (o[1].x + o[1].y), s * (o[1].y - o[1].x)};   // e^{-i pi/4}
-  o[2] = cmul_mi(o[2]);                                      // e^{-i pi/2}
-  o[3] = {s * (o[3].y - o[3].x), -s * (o[3].x + o[3].y)};  // e^{-3i pi/4}
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    v[q] = cadd(e[q], o[q]);
-    v[q + 4] = csub(e[q], o[q]);
-  }
-}
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// one Stockham pass of radix R over an N2-point sequence: sub-transforms of Ns -> Ns * R
-// points (twiddle e^{-2 pi i r k / (Ns R)} = tw[2 r k N2 / (Ns R) mod N], tw[t] =
-// e^{-2 pi i t / N}, N = 2 N2)
-template <int R>
-__device__ __forceinline__ void stockham_pass(const cd* __restrict__ src, cd* __restrict__ dst,
-                                              int N2, int Ns, const cd* __restrict__ tw,
-                                              int lane) {
-  const int nb = N2 / R;
-  const int tstep = 2 * (N2 / (Ns * R));
-  for (int j = lane; j < nb; j += 64) {
-    const int k = j & (Ns - 1);
-    cd v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) v[r] = src[j + r * nb];
-    if (Ns > 1) {
-#pragma unroll
-      for (int r = 1; r < R; ++r) v[r] = cmul(v[r], tw[(r * k * tstep) & (2 * N2 - 1)]);
-    }
-    dft_r<R>(v);
-    const int base = (j - k) * R + k;
-#pragma unroll
-    for (int q = 0; q < R; ++q) dst[base + q * Ns] = v[q];
-  }
-}
-
+// The FFT helpers (cd, dft_r, stockham_pass, wave_sync) are in fft_f64.h, shared with
+// release_mel_fft (release_mel.hip).
 __global__ void __launch_bounds__(256)
 logmel_fft(const float* __restrict__ wav, int64_t n_samp, int n_fft, int hop, int n_frames,
            int fpw, const float* __restrict__ window, const cd* __restrict__ tw,

@@ -42,6 +42,26 @@ def vocode_list(gen, mels: Sequence[torch.Tensor]) -> List[torch.Tensor]:
     return [wav[b, 0, :gen.output_length(lens[b])] for b in range(len(mels))]
 
 
+def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor:
+    """Copy-synthesis on the device: wav [B, N] → ``frontend`` (``mel.ReleaseMelSpectrogram``)
+    → ``gen`` → wav [B, 1, (N // hop) * hop].  With ``lengths`` (valid samples per item of a
+    padded batch) the front end's frame counts go to the Generator as a device tensor — no
+    host round trip — so item b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``."""
+    import math
+    hop = math.prod(int(u) for u in gen._hfg_args[1])
+    if frontend.hop_size != hop:
+        raise ValueError(f"front end hop_size {frontend.hop_size} != the Generator's "
+                         f"prod(upsample_rates) {hop}")
+    if frontend.num_mels != gen.n_mels:
+        raise ValueError(f"front end num_mels {frontend.num_mels} != the Generator's "
+                         f"n_mels {gen.n_mels}")
+    with torch.no_grad():
+        if lengths is None:
+            return gen(frontend(wav))
+        mel, frame_lengths = frontend(wav, lengths)
+        return gen(mel, lengths=frame_lengths)
+
+
 class StreamingVocoder:
     """Chunked vocoding of growing mel streams with bounded state (SURVEY.md §8(f) 3;
     the reference's Requirement 18, ``.kiro/specs/tts-sam-bert-hifigan/requirements.md:

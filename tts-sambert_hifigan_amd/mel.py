@@ -14,6 +14,9 @@ The arithmetic runs in the HIP kernels of ``libhifigan_hip.so``: one launch of a
 FFT with a float64 spectrum + mel projection + log (:class:`MelSpectrogram`, the batched
 ``[B, N] → [B, n_mels, N // hop + 1]`` form that feeds ``HiFiGANGenerator``), and the
 polyphase sinc resampler (:class:`Resample`, torchaudio ``Resample`` defaults).
+:class:`ReleaseMelSpectrogram` is the public HiFi-GAN release's ``mel_spectrogram``
+(``center=False`` framing, ``ln`` of the clipped magnitude mel, librosa's filterbank from
+:func:`librosa_mel_fn`; ragged batches), the mel its checkpoints expect.
 There is no CPU fallback: a CPU waveform raises.
 """
 from __future__ import annotations
@@ -28,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .hifigan import _lengths_on
 
 
 def _check_mel(lib, rc):
@@ -174,6 +178,143 @@ class MelSpectrogram:
             ctypes.c_void_p(ws.data_ptr()), ws_bytes,
             ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
         return mel
+
+
+def librosa_mel_fn(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: Optional[float]
+                   ) -> np.ndarray:
+    """``librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)`` (Slaney scale, Slaney norm) as
+    the release's ``meldataset.py`` calls it: float32 ``[n_mels, n_fft // 2 + 1]``, evaluated
+    in float64 from the published definition (librosa is not a dependency)."""
+    if fmax is None:
+        fmax = sr / 2.0
+    fftfreqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
+
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+
+    def hz_to_mel(f):
+        return min_log_mel + np.log(f / min_log_hz) / logstep if f >= min_log_hz else f / f_sp
+
+    mels = np.linspace(hz_to_mel(float(fmin)), hz_to_mel(float(fmax)), n_mels + 2)
+    mel_f = np.where(mels >= min_log_mel, min_log_hz * np.exp(logstep * (mels - min_log_mel)),
+                     f_sp * mels)                       # mel_frequencies(n_mels + 2)
+    fdiff = np.diff(mel_f)
+    ramps = np.subtract.outer(mel_f, fftfreqs)
+    weights = np.zeros((n_mels, 1 + n_fft // 2))
+    for i in range(n_mels):
+        lower = -ramps[i] / fdiff[i]
+        upper = ramps[i + 2] / fdiff[i + 1]
+        weights[i] = np.maximum(0.0, np.minimum(lower, upper))
+    weights *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+    return weights.astype(np.float32)
+
+
+class ReleaseMelSpectrogram:
+    """The public HiFi-GAN release's ``meldataset.mel_spectrogram`` on the HIP device (the
+    mel every released ``generator_v*`` checkpoint expects): reflect pad of
+    ``(n_fft - hop_size) / 2`` a side, ``torch.stft(center=False)`` with the periodic Hann
+    window, ``sqrt(re² + im² + 1e-9)``, the librosa filterbank, ``ln(max(mel, 1e-5))``.
+    ``wav [B, N]`` → ``mel [B, num_mels, N // hop_size]`` in one launch (release_mel_fft,
+    float64 spectrum).  :class:`MelSpectrogram` is the reference's torchaudio framing, a
+    different quantity (one frame more, log10 of power).
+
+    ``n_fft`` must be a power of two >= 16 and ``n_fft - hop_size`` even; anything else is
+    refused by the constructor.  With ``lengths`` (valid samples per item of a padded batch)
+    item b is framed as if it were alone with ``lengths[b]`` samples, its columns past
+    ``lengths[b] // hop_size`` hold ``ln(1e-5)`` (the mel of silence), samples past its length
+    are never read, and the call also returns the frame counts as a device int32 tensor —
+    ready to be the Generator's ``lengths``.  There is no CPU fallback."""
+
+    def __init__(self, sampling_rate: int = 22050, n_fft: int = 1024, hop_size: int = 256,
+                 win_size: int = 1024, num_mels: int = 80, fmin: float = 0.0,
+                 fmax: Optional[float] = 8000.0, device=None):
+        self.lib = _lib.load_library()
+        c = _lib.HfgRelmelConfig()
+        c.sampling_rate, c.n_fft, c.hop_size, c.win_size, c.num_mels = (
+            int(sampling_rate), int(n_fft), int(hop_size), int(win_size), int(num_mels))
+        c.fmin = float(fmin)
+        c.fmax = 0.0 if fmax is None else float(fmax)   # 0: sampling_rate / 2 (config null)
+        self.cfg = c
+        self.sampling_rate, self.n_fft, self.hop_size = int(sampling_rate), int(n_fft), int(hop_size)
+        self.win_size, self.num_mels = int(win_size), int(num_mels)
+        self.pad = (self.n_fft - self.hop_size) // 2
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        h = ctypes.c_void_p()
+        _check_mel(self.lib, self.lib.hfg_relmel_create(ctypes.byref(c), self.device.index or 0,
+                                                        ctypes.byref(h)))
+        self.ptr = h
+        # the release's float32 window (torch.hann_window, centred by torch.stft) and
+        # librosa's filterbank, stored [n_fft/2+1, num_mels] as the kernel reads it
+        self._window = stft_window(self.n_fft, self.win_size).contiguous()
+        self._fb = torch.from_numpy(np.ascontiguousarray(
+            librosa_mel_fn(self.sampling_rate, self.n_fft, self.num_mels, fmin, fmax).T))
+        fp = ctypes.POINTER(ctypes.c_float)
+        _check_mel(self.lib, self.lib.hfg_relmel_set_tables(
+            self.ptr, ctypes.cast(self._window.data_ptr(), fp),
+            ctypes.cast(self._fb.data_ptr(), fp)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "ptr", None):
+                self.lib.hfg_relmel_destroy(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+    def filterbank(self) -> torch.Tensor:
+        """The [n_fft/2+1, num_mels] filterbank the device uses (librosa's, transposed)."""
+        return self._fb.clone()
+
+    def window(self) -> torch.Tensor:
+        """The [n_fft] window the device uses (torch.hann_window(win_size), centred)."""
+        return self._window.clone()
+
+    def frames(self, n_samples: int) -> int:
+        """Frames of an n_samples item: n // hop_size, or -1 when it has none (n <= the
+        reflect pad, or n < hop_size)."""
+        return int(self.lib.hfg_relmel_frames(self.ptr, int(n_samples)))
+
+    def __call__(self, wav: torch.Tensor, lengths=None):
+        """wav [B, N] float32 on the HIP device → mel [B, num_mels, N // hop_size]; with
+        ``lengths`` (sequence of ints or an int tensor, [B]) → (mel, frame_lengths int32 [B]
+        on the device).  Host lengths are validated here; a device tensor is not read back
+        (the kernel clamps it into [0, N])."""
+        if not wav.is_cuda:
+            raise RuntimeError("ReleaseMelSpectrogram (MI355X) needs a HIP tensor; no CPU fallback")
+        if wav.dim() != 2:
+            raise RuntimeError("expected wav [B, N]")
+        B, N = wav.shape
+        T = self.frames(N)
+        if B == 0 or T < 1:
+            raise RuntimeError(f"wav [{B}, {N}] has no frame: N must exceed the reflect pad "
+                               f"{self.pad} and be at least hop_size {self.hop_size}")
+        lens_t = None
+        if lengths is not None:
+            on_device = isinstance(lengths, torch.Tensor) and lengths.is_cuda
+            if not on_device:
+                host = torch.as_tensor(lengths)
+                if host.shape != (B,):
+                    raise RuntimeError(f"lengths must have shape [{B}]")
+                if any(self.frames(int(n)) < 1 or int(n) > N for n in host.tolist()):
+                    raise RuntimeError(f"every length must be in ({self.pad}, {N}] and at "
+                                       f"least hop_size {self.hop_size}, got {host.tolist()}")
+            lens_t = _lengths_on(lengths, wav.device)
+            if lens_t.shape != (B,):
+                raise RuntimeError(f"lengths must have shape [{B}]")
+        wav = wav.detach().to(torch.float32).contiguous()
+        mel = torch.empty(B, self.num_mels, T, device=wav.device, dtype=torch.float32)
+        frame_lens = (torch.empty(B, device=wav.device, dtype=torch.int32)
+                      if lens_t is not None else None)
+        with torch.cuda.device(wav.device):
+            _check_mel(self.lib, self.lib.hfg_relmel_forward(
+                self.ptr, ctypes.c_void_p(wav.data_ptr()), B, N,
+                ctypes.c_void_p(lens_t.data_ptr()) if lens_t is not None else None,
+                ctypes.c_void_p(mel.data_ptr()),
+                ctypes.c_void_p(frame_lens.data_ptr()) if frame_lens is not None else None,
+                ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+        return mel if lens_t is None else (mel, frame_lens)
 
 
 class Resample:
