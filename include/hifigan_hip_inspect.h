@@ -57,6 +57,20 @@ int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen);
  * less twice the stage's largest thin_halo.  0 when there is no such kernel. */
 int hfg_debug_thin_window(int C, int mfma);
 
+/* Dynamic-LDS bytes the launcher of a kernel family requests for a launch with the given
+ * integer arguments (no handle, no device), so the host suite can pin every kernel's LDS
+ * layout (tests/golden/lds_index.json).  family and args[n_args]:
+ *   "conv_bf16x3"      {tile, taps, dilation, LDS-staged epilogue 0|1}
+ *   "ups_bf16x3"       {configuration}
+ *   "resblock_bf16x3"  {channels, window columns, convs of the launch}  (both ResBlock kernels)
+ *   "mrf_thin", "mrf_thin_mfma"  {channels}
+ *   "conv1d_mfma_f32"  {tile, taps, dilation}
+ *   "conv_post"        {channels}
+ *   "logmel_fft"       {n_fft, hop, n_mels, frames per wave}  (also release_mel_fft)
+ * -1 for an unknown family, a wrong argument count, or arguments the family has no kernel
+ * for. */
+int64_t hfg_debug_lds_bytes(const char* family, const int* args, int n_args);
+
 /* A Generator forward (one stream) that also copies the stage outputs the
  * reference's forward passes through (models/hifigan.py:238-251) into
  * caller-owned device buffers: taps[0] <- conv_pre [B][C0][T], taps[1 + 2i] <-

@@ -2,6 +2,7 @@
 """Compare the gfx950 device assembly of two source trees, kernel by kernel (CPU only).
 
     python tests/tools/isa_diff.py OLD_TREE NEW_TREE [--jobs N] [--work DIR]
+                                   [--define NAME=VALUE ...]
 
 A refactor of the kernel translation units must leave every kernel's code unchanged
 (csrc/resblock_body.h records how little it takes to move the register allocation).  For
@@ -13,7 +14,9 @@ sides' register counts, scratch and LDS size from the code-object metadata.
 
 Exit status 0: every file of both trees identical; 1: any difference (a kernel or file on
 one side only included); 2: a compile failed.  --work keeps the assembly (<work>/a, <work>/b)
-and reuses a file whose source, headers and flags are unchanged.
+and reuses a file whose source, headers and flags are unchanged.  --define (repeatable) appends
+-DNAME=VALUE to both trees' flags, to compare the diagnostic builds (HFG_ABLATE=1,
+HFG_CONV_TIMING=1) as well.
 """
 from __future__ import annotations
 
@@ -120,6 +123,8 @@ def main() -> int:
     ap.add_argument("new_tree")
     ap.add_argument("--jobs", type=int, default=MAX_JOBS)
     ap.add_argument("--work", help="directory that keeps the assembly between runs")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME=VALUE",
+                    help="append -DNAME=VALUE to both trees' flags (repeatable)")
     args = ap.parse_args()
     jobs = max(1, min(args.jobs, MAX_JOBS))
 
@@ -132,6 +137,7 @@ def main() -> int:
     sides = []
     for tag, tree in (("a", args.old_tree), ("b", args.new_tree)):
         build = load_build(os.path.abspath(tree))
+        build.FLAGS = [*build.FLAGS, *("-D" + d for d in args.define)]
         out_dir = os.path.join(work, tag)
         os.makedirs(out_dir, exist_ok=True)
         sides.append((build, out_dir, [s for s in build.SOURCES if s.endswith(".hip")]))

@@ -192,6 +192,7 @@ SIGNATURES = {
                                           POINTER(c_int64)]),
     "hfg_debug_plan": (c_int, [c_void_p, c_char_p, c_size_t]),
     "hfg_debug_thin_window": (c_int, [c_int, c_int]),
+    "hfg_debug_lds_bytes": (c_int64, [c_char_p, POINTER(c_int), c_int]),
     "hfg_mrf_create": (c_int, [POINTER(HfgMrfConfig), c_int, POINTER(c_void_p)]),
     "hfg_mrf_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
     "hfg_mrf_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,

@@ -20,10 +20,6 @@
 // is multiplied), one barrier per chunk.  Epilogue identical to conv1d_mfma_f32.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
-#include <algorithm>
-
 #include <cstdio>
 #include <type_traits>
 
@@ -67,17 +63,24 @@ template <int KT_, int TPC, int WAVES_M, int WAVES_N, int WM, int WN, int WD, bo
 __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, 2)
 conv1d_bf16x3(const ConvParams p) {
   static_assert(!AREG || (KT_ > 0 && !UPS && WM * WN >= 8), "AREG: compile-time taps, layer convs");
+  // two weight slabs: chunk c + 1 lands while chunk c is multiplied (the three-deep ring went
+  // with tile 0)
+  static_assert(WD == 2, "two-slab weight ring");
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int NT = 64 * NW;
   constexpr int MT = 32 * WM * WAVES_M;
   constexpr int NTILE = 32 * WN * WAVES_N;
-  constexpr int XROW = 16;  // bf16 per staged row: 16 channels (32 B), 16-B halves XOR-swizzled
-  constexpr int TAP_ELEMS = 2 * WAVES_M * WM * 64 * 8;  // bf16 per tap of a slab (hi+lo)
-  constexpr int SLAB = TPC * TAP_ELEMS;           // bf16 per chunk slab
   constexpr int KT_MAX = KT_ > 0 ? KT_ : 16;
-  constexpr int XW_MAX = NTILE + ((KT_MAX - 1) * kMaxDil < kBf16x3MaxHalo
-                                       ? (KT_MAX - 1) * kMaxDil : kBf16x3MaxHalo);
-  constexpr int XQ = (2 * XW_MAX + NT - 1) / NT;  // staging tasks per thread
+  // the LDS carve-up (lds_layout.h; the host sizes the launch from the same value): LY the
+  // parts fixed by the instantiation, at its widest window
+  constexpr Bf16x3Cfg TCFG{WAVES_M, WAVES_N, WM, WN, TPC, WD, AREG ? 1 : 0};
+  constexpr ConvBf16x3Lds LY = conv_bf16x3_lds(TCFG, KT_MAX, 0);
+  static_assert(conv_bf16x3_lds(TCFG, KT_MAX, LY.xw_max).total(!UPS) <= (int)kMaxLdsBytes, "LDS");
+  constexpr int XROW = kBf16x3XRow;  // bf16 per staged row, 16-B halves XOR-swizzled
+  constexpr int SLAB = LY.slab;                   // bf16 per chunk slab
+  constexpr int TAP_ELEMS = SLAB / TPC;           // bf16 per tap of a slab (hi+lo)
+  constexpr int XW_MAX = LY.xw_max;
+  constexpr int XQ = LY.xq;                       // staging tasks per thread
   static_assert(XQ * 8 <= 32, "ok mask");
   constexpr int NX = XQ * 8;                      // input loads per thread per channel group
   constexpr int PW = SLAB / 8 / 64 / NW;          // LDS-DMA pieces per thread per slab
@@ -90,17 +93,14 @@ conv1d_bf16x3(const ConvParams p) {
   // AREG: the planes hold a row for every staging task (XQ*NT/2 >= XW_MAX rows), so
   // store_x writes all its tasks unconditionally (rows >= XW are never read) and stays
   // straight-line code the tap schedule interleaves into the MFMA stream
-  constexpr int XROWS_AREG = XQ * NT / 2;
-  static_assert(XROWS_AREG >= XW_MAX, "AREG planes");
-  // AREG half planes (8 channels, 16-B rows) padded by 64 B: a ds_write_b128 lane group
-  // (8 lanes: 4 rows of each half) then covers the 32 write banks once
-  constexpr int HPS_AREG = XROWS_AREG * 8 + 32;
-  const int xplane = AREG ? 2 * HPS_AREG : (XW * XROW + 7) & ~7;  // bf16 per X plane
+  static_assert(LY.xrows >= XW_MAX, "AREG planes");
+  constexpr int HPS_AREG = LY.hps;                // AREG half plane (8 channels, 16-B rows)
+  const int xplane = AREG ? LY.xplane : bf16x3_xplane(XW);  // bf16 per X plane
   const int xbuf = 2 * xplane;                    // hi + lo planes
 
   extern __shared__ __attribute__((aligned(16))) __bf16 lds16[];
   __bf16* const Wbuf0 = lds16;
-  __bf16* const Xbuf0 = lds16 + (AREG ? 0 : WD * SLAB);
+  __bf16* const Xbuf0 = lds16 + LY.x_off;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -391,18 +391,19 @@ conv1d_bf16x3(const ConvParams p) {
   tsv[12] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
             ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
   cstamp(1);
+  uint64_t* const epi_ts = tsv;  // the epilogue's stamps (conv_epilogue_lds2)
 #else
   auto cstamp = [](int) {};
+  constexpr uint64_t* epi_ts = nullptr;
 #endif
   // AREG: the m-tile's bias in LDS for the epilogue (conv_epilogue_lds2), visible after the
   // prologue barrier
-  // the AREG tiles (5, 6): the host sizes the LDS from the same configuration
-  constexpr Bf16x3Cfg TCFG{WAVES_M, WAVES_N, WM, WN, TPC, WD, AREG ? 1 : 0};
-  constexpr int BIAS_OFF = AREG ? bf16x3_areg_bias_off(KT_MAX, TCFG) : 0;
+  constexpr int BIAS_OFF = AREG ? LY.bias_off : 0;
   float* const bias_lds = reinterpret_cast<float*>(reinterpret_cast<char*>(lds16) + BIAS_OFF);
   if constexpr (AREG)
     for (int i = tid; i < MT; i += NT) bias_lds[i] = p.bias[mt * MT + i];
-  // ---- prologue: weight slabs of chunks 0..WD-2, input window of channel group 0 ----
+  // ---- prologue: weight slab of chunk 0, input window of channel group 0 ----
+  // (the one-trip loop stays: as a plain `if` the statement compiles to other code)
   load_x(0);
   if constexpr (!AREG) {
 #pragma unroll
@@ -559,16 +560,14 @@ conv1d_bf16x3(const ConvParams p) {
     // phase in which both waves of a SIMD leave the pipe idle.  The last group re-stages
     // itself into the idle buffer (no branch; one group of extra loads per block).
     // Ablation bit0 (no restaging) is not available on this path.
-    static_assert(WD == 2, "fast path: two-slab weight ring");
     constexpr int NTG = (KT_ + TPC - 1) / TPC;
     constexpr int XG = NTG >= 2 ? NTG - 2 : 0;
     using I6 = std::integral_constant<int, 6>;
     using I3 = std::integral_constant<int, 3>;
     using I0 = std::integral_constant<int, 0>;
-    // every other tap stream pinned too: the next column tile's B reads issue after the
-    // current tile's first MFMA, not after its last (the default schedule waits on them
-    // right before use: one exposed LDS round trip per column tile)
-    constexpr bool p_pin = true;
+    // (every tap stream is pinned, the plain ones with I0: the next column tile's B reads
+    // issue after the current tile's first MFMA, not after its last -- the default schedule
+    // waits on them right before use: one exposed LDS round trip per column tile)
     using T_ = std::true_type;
     using F_ = std::false_type;
     const int NG = p.n_chunks / NTG;
@@ -604,14 +603,14 @@ conv1d_bf16x3(const ConvParams p) {
           issue_next_w();
           if (ISX) load_x(gn);
           tap_stream(Ws, Xh, 0, tap0);
-          if constexpr (p_pin) pin_stream(I0{}, F_{}, F_{});
+          pin_stream(I0{}, F_{}, F_{});
           if (STX) store_x(Xn);
         }
 #pragma unroll
         for (int jj = 1; jj < TPC; ++jj)
           if (jj < nt) {
             tap_stream(Ws, Xh, jj, tap0 + jj);
-            if constexpr (p_pin) pin_stream(I0{}, F_{}, F_{});
+            pin_stream(I0{}, F_{}, F_{});
           }
         // the slab of chunk c+1 must have landed; younger: this chunk's input loads
         if (ISX && !STX) wait_x(std::integral_constant<int, NX>{});
@@ -621,12 +620,12 @@ conv1d_bf16x3(const ConvParams p) {
       }
     }
   } else {
-  // chunk c = (channel group g, tap group tg).  Weights: a ring of WD slabs, chunk c+WD-1
-  // issued while chunk c is multiplied.  Input window: double-buffered per channel
+  // chunk c = (channel group g, tap group tg).  Weights: two slabs, chunk c+1 issued
+  // while chunk c is multiplied.  Input window: double-buffered per channel
   // group; group g+1's loads are issued at tap group xg = max(n_tg-2, 0) of group g
   // and land in LDS at the group's last tap group.
   const int xg = n_tg >= 2 ? n_tg - 2 : 0;
-  int wslot = 0;                                  // ring slot of chunk c
+  int wslot = 0;                                  // slab of chunk c
   for (int c = 0; c < p.n_chunks; ++c) {
     const int g = c / n_tg, tg = c - (c / n_tg) * n_tg;
     const __bf16* Ws = Wbuf0 + wslot * SLAB;
@@ -635,17 +634,15 @@ conv1d_bf16x3(const ConvParams p) {
     const bool issue_x = more_groups && tg == xg && !(kAblate && (p.dbg & 1));
     const bool store_now = more_groups && tg == n_tg - 1 && !(kAblate && (p.dbg & 1));
     // always PW pieces per thread, so every vmcnt below is a constant: past the last
-    // chunk the last slab is re-read into the free slot (that of chunk c-1)
+    // chunk the last slab is re-read into the free slot (that of chunk c-1).  (The slot
+    // steps and wraps at 2 here; toggling it, wslot ^ 1 as in the unrolled loop above,
+    // is other device code: DESIGN.md)
     auto issue_next_w = [&]() {
-      int s2 = wslot + WD - 1;
-      if (s2 >= WD) s2 -= WD;
-      issue_w(min(c + WD - 1, p.n_chunks - 1), Wbuf0 + s2 * SLAB);
+      int s2 = wslot + 1;
+      if (s2 >= 2) s2 -= 2;
+      issue_w(min(c + 1, p.n_chunks - 1), Wbuf0 + s2 * SLAB);
     };
-    // with a deeper ring, the chunk that stores the next input window issues its slab
-    // after that store: the compiler's vmcnt(0) for the input registers then does not
-    // also wait for the new slab
-    const bool w_late = WD > 2 && store_now;
-    if (!w_late) issue_next_w();
+    issue_next_w();
     // after the slab DMA (kept older by the sched barrier): a vmcnt can wait for it, not
     // for these
     __builtin_amdgcn_sched_barrier(0);
@@ -672,14 +669,12 @@ conv1d_bf16x3(const ConvParams p) {
       }
     }
     if (store_now) store_x(Xbuf0 + ((g + 1) & 1) * xbuf);
-    if (w_late) issue_next_w();
-    // the slab of chunk c+1 must have landed.  Younger than it: the slabs of chunks
-    // c+2..c+WD-1 (PW pieces each) and this chunk's input loads when a later chunk
-    // consumes them.
-    if (issue_x && !store_now) wait_x(std::integral_constant<int, NX + PW * (WD - 2)>{});
-    else wait_vm<PW * (WD - 2)>();
+    // the slab of chunk c+1 must have landed.  Younger than it: this chunk's input loads
+    // when a later chunk consumes them.
+    if (issue_x && !store_now) wait_x(std::integral_constant<int, NX>{});
+    else wait_vm<0>();
     if (!(kAblate && (p.dbg & 4))) lds_barrier();
-    if (++wslot == WD) wslot = 0;
+    if (++wslot == 2) wslot = 0;
   }
   }
   if (kAblate && (p.dbg & 8)) {  // ablation: no epilogue
@@ -785,20 +780,15 @@ conv1d_bf16x3(const ConvParams p) {
     // sized the LDS for it (p.epi_lds); the accumulator-layout epilogue otherwise
     if (p.epi_lds && (p.N & 3) == 0) {
       // every wave is done with the weight slabs and input windows, and no weight-slab
-      // LDS-DMA is still in flight (a deeper ring leaves the re-read past-the-end slabs
-      // outstanding; they count in vmcnt, not lgkmcnt)
+      // LDS-DMA is still in flight (it counts in vmcnt, not lgkmcnt)
       wait_vm<0>();
       lds_barrier();
       cstamp(7);
-      float* stage = reinterpret_cast<float*>(lds16) + wave * 32 * (32 * WN + 8);
+      float* stage = reinterpret_cast<float*>(lds16) + wave * epi_stage_wave(WN);
       if constexpr (AREG)
         conv_epilogue_lds2<WM, WN>(p, acc, b, mt * MT + wave_m * 32 * WM, mt * MT,
                                    n0 + wave_n * 32 * WN, N_b, half, col, stage, bias_lds, lane,
-#if HFG_CONV_TIMING
-                                   sc, tsv);
-#else
-                                   sc);
-#endif
+                                   sc, epi_ts);
       else
         conv_epilogue_lds<WM, WN>(p, acc, b, mt * MT + wave_m * 32 * WM, n0 + wave_n * 32 * WN,
                                   N_b, half, col, stage, lane, sc);
@@ -859,15 +849,11 @@ Entry3 g_entries3[] = {
 
 }  // namespace
 
-size_t bf16x3_lds_bytes(int tile, int kt, int dil) {
+// the AREG instances are compiled for their taps (kt_max = kt); the others size their windows
+// from the launch's taps and dilation
+size_t bf16x3_lds_bytes(int tile, int kt, int dil, bool epi_lds) {
   const Bf16x3Cfg& t = kBf16x3Tiles[tile];
-  // bf16: taps x planes x rows x 16 ch (no slab ring on the AREG tile)
-  const size_t slab = t.AREG ? 0 : (size_t)t.TPC * 2 * t.MT() * 16;
-  // AREG: a plane row per staging task (the kernel's XROWS_AREG)
-  const int xw = t.AREG ? bf16x3_areg_rows(kt, t) : t.NTILE() + (kt - 1) * dil;
-  // AREG: two padded half planes (the kernel's HPS_AREG)
-  const size_t xplane = t.AREG ? (size_t)xw * 16 + 64 : ((size_t)xw * 16 + 7) & ~(size_t)7;
-  return sizeof(__bf16) * (t.WD * slab + 2 * 2 * xplane);  // weight ring + 2 (hi,lo) windows
+  return (size_t)conv_bf16x3_lds(t, kt, bf16x3_xw(t, kt, dil)).total(epi_lds);
 }
 
 hipError_t launch_conv_bf16x3(int tile, int kt, bool ups, int fmt, int np, const ConvParams& p,
@@ -885,11 +871,7 @@ hipError_t launch_conv_bf16x3(int tile, int kt, bool ups, int fmt, int np, const
   if (p.dil > kMaxDil || (e->kt == 0 && kt > 16) || (kt - 1) * p.dil > kBf16x3MaxHalo)
     return hipErrorInvalidValue;
   const Bf16x3Cfg& t = kBf16x3Tiles[tile];
-  size_t lds = bf16x3_lds_bytes(tile, kt, p.dil);
-  if (p.epi_lds && !ups)
-    lds = std::max(lds, (size_t)t.threads() / 64 * 32 * (32 * t.WN + 8) * sizeof(float));
-  // AREG: + the m-tile's bias copy (its kernel instance is compiled for its KT)
-  if (t.AREG) lds = (size_t)bf16x3_areg_bias_off(e->kt, t) + (size_t)t.MT() * sizeof(float);
+  const size_t lds = bf16x3_lds_bytes(tile, kt, p.dil, p.epi_lds && !ups);
   auto fmt_name = [&](char* s, size_t n) {
     snprintf(s, n, "conv1d_bf16x3<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %d>", e->kt, t.TPC,
              t.WAVES_M, t.WAVES_N, t.WM, t.WN, t.WD, e->ups ? "true" : "false", e->np,

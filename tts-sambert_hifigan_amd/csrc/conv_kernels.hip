@@ -59,10 +59,10 @@ conv1d_mfma_f32(const ConvParams p) {
   constexpr int XQ = (CK * (NTILE + halo_max(KT_)) + NT - 1) / NT;
   const int KT = KT_ > 0 ? KT_ : p.kt;
   const int XW = NTILE + (KT - 1) * p.dil;
-  const int nx = CK * XW;
+  const int nx = conv_f32_nx(CK, XW);         // (the LDS terms: lds_layout.h)
   const float inv_xw = 1.0f / (float)XW;
-  const int wchunk = MT * CK * KT;            // floats per weight slab
-  const int stage_sz = wchunk + ((nx + 3) & ~3);
+  const int wchunk = conv_f32_wchunk(MT, CK, KT);  // floats per weight slab
+  const int stage_sz = conv_f32_stage(wchunk, nx);
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
 
@@ -238,7 +238,7 @@ conv1d_mfma_f32(const ConvParams p) {
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     conv_epilogue_lds<WM, WN>(p, acc, b, mt * MT + wave_m * 32 * WM, n0 + wave_n * 32 * WN, N_b,
-                              half, col, lds + (threadIdx.x >> 6) * 32 * (32 * WN + 8),
+                              half, col, lds + (threadIdx.x >> 6) * 32 * epi_stage_row(WN),
                               threadIdx.x & 63);
   } else {
     conv_epilogue<WM, WN>(p, acc, b, mt * MT + wave_m * 32 * WM, n0 + wave_n * 32 * WN, N_b,
@@ -253,12 +253,12 @@ __global__ void __launch_bounds__(256)
 conv_post_tanh(const float* __restrict__ x, int64_t x_bs, int C, int L, const float* __restrict__ w,
                const float* __restrict__ bias, float* __restrict__ wav,
                const int32_t* __restrict__ lens, float slope) {
-  constexpr int TT = 256, KP = 7, HALO = 3;
-  constexpr int XW = TT + KP - 1;
+  constexpr int TT = kConvPostTile, KP = kConvPostTaps, HALO = 3;
+  constexpr int XW = kConvPostXw;
   constexpr int CBLK = kConvPostCB;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Ws = lds;              // C*7
-  float* Xs = lds + ((C * KP + 3) & ~3);  // CBLK*XW
+  float* Xs = lds + conv_post_x_off(C);  // CBLK*XW (lds_layout.h)
   const int t0 = blockIdx.x * TT;
   const int b = blockIdx.y;
   const float* xb = x + (int64_t)b * x_bs;
@@ -408,6 +408,12 @@ struct Entry {
 #define HFG_ENTRIES_KT(KT, UPS) \
   HFG_ENTRY(KT, 0, UPS), HFG_ENTRY(KT, 1, UPS), HFG_ENTRY(KT, 2, UPS)
 
+// dynamic LDS of the instance compiled for dkt taps (0: runtime taps) running kt taps
+size_t f32_lds_bytes(int tile, int dkt, int kt, int dil) {
+  const TileCfg& t = kTiles[tile];
+  return conv_f32_lds_total(t.MT(), ck_for(dkt, tile), kt, t.NTILE() + (kt - 1) * dil);
+}
+
 Entry g_entries[] = {
     HFG_ENTRIES_KT(3, false), HFG_ENTRIES_KT(5, false), HFG_ENTRIES_KT(7, false),
     HFG_ENTRIES_KT(11, false), HFG_ENTRIES_KT(2, false), HFG_ENTRIES_KT(0, false),
@@ -430,13 +436,10 @@ hipError_t launch_conv(TileId tile, int kt, bool ups, const ConvParams& p, int n
   const TileCfg& t = kTiles[tile];
   const int ck = ck_for(e->kt, tile);
   if ((kt - 1) * p.dil > halo_max(e->kt)) return hipErrorInvalidValue;
-  const int xw = t.NTILE() + (kt - 1) * p.dil;
-  const size_t stage = (size_t)t.MT() * ck * kt + (((size_t)ck * xw + 3) & ~(size_t)3);
-  size_t lds = sizeof(float) * 2 * stage;
+  const size_t lds = f32_lds_bytes(tile, e->kt, kt, p.dil);
   // the LDS-staged epilogue only where its staging fits the main loop's footprint
   ConvParams pe = p;
-  const size_t epi = sizeof(float) * (size_t)t.threads() / 64 * 32 * (32 * t.WN + 8);
-  if (ups || epi > lds) pe.epi_lds = 0;
+  if (ups || epi_stage_bytes(t.threads(), t.WN) > lds) pe.epi_lds = 0;
   auto fmt_name = [&](char* s, size_t n) {
     snprintf(s, n, "conv1d_mfma_f32<%d, %d, %d, %d, %d, %d, %s>", e->kt, t.WM, t.WN, t.WAVES_M,
              t.WAVES_N, ck, e->ups ? "true" : "false");
@@ -601,11 +604,12 @@ hipError_t launch_absmax(const float* x, int64_t x_bs, int64_t x_cs, int64_t x_t
 bool fp32_conv_supported(int tile, int kt, int dil) {
   const int dkt = dispatch_kt(kt);
   if (kt < 1 || dil < 1 || (kt - 1) * dil > halo_max(dkt)) return false;
-  const TileCfg& t = kTiles[tile];
-  const int ck = ck_for(dkt, tile);
-  const int xw = t.NTILE() + (kt - 1) * dil;
-  const size_t stage = (size_t)t.MT() * ck * kt + (((size_t)ck * xw + 3) & ~(size_t)3);
-  return sizeof(float) * 2 * stage <= kMaxLdsBytes;
+  return fp32_conv_lds_bytes(tile, kt, dil) <= kMaxLdsBytes;
+}
+
+// a layer conv of kt taps runs on the instance of dispatch_kt(kt)
+size_t fp32_conv_lds_bytes(int tile, int kt, int dil) {
+  return f32_lds_bytes(tile, dispatch_kt(kt), kt, dil);
 }
 
 // Order-independent 32-bit content hash of fp32 tensors (the drop-in module's check that

@@ -159,19 +159,19 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, floatx16e (&a
 }
 
 // The same contract with the tile staged through LDS: each wave writes 32 accumulator
-// rows x 32*WN columns at a time into its own LDS region (row stride 32*WN + 8 floats:
-// the two row quads a ds_write_b32 touches land 32 banks apart) and reads them back as
+// rows x 32*WN columns at a time into its own LDS region (row stride epi_stage_row(WN),
+// lds_layout.h: the two row quads a ds_write_b32 touches land 32 banks apart) and reads them back as
 // row-contiguous float4, so the residual / MRF loads and the stores are 16-B per lane
 // and fully coalesced (4x fewer memory instructions than the accumulator layout's
 // one-dword-per-row stores).  Needs N % 4 == 0 (16-B aligned rows) and
-// 32 * (32*WN + 8) * 4 bytes of LDS per wave at `stage`; the caller has barriered the
+// epi_stage_wave(WN) floats of LDS per wave at `stage`; the caller has barriered the
 // block (every wave is done with the main loop's LDS).
 template <int WM, int WN>
 __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, floatx16e (&acc)[WM][WN],
                                                   int b, int row_base, int n_base, int N_b,
                                                   int half, int col, float* stage, int lane,
                                                   float sc = 1.0f) {
-  constexpr int SROW = 32 * WN + 8;
+  constexpr int SROW = epi_stage_row(WN);
   constexpr int C4 = 8 * WN;                 // float4 per staged row
   const int64_t bo = (int64_t)b * p.y_bs;
   const float* resb = p.res ? p.res + bo : nullptr;
@@ -324,7 +324,7 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
   auto ts = [&](int s_) {
     if (tsv) tsv[s_] = __builtin_amdgcn_s_memtime();
   };
-  constexpr int SROW = 32 * WN + 8;
+  constexpr int SROW = epi_stage_row(WN);
   constexpr int C4 = 8 * WN;                 // float4 per staged row
   constexpr int IT = 32 * C4 / 64;           // float4 per lane and row tile
   const int64_t bo = (int64_t)b * p.y_bs;

@@ -270,7 +270,7 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     p.amax_out = last ? aout : nullptr;
     p.dbg = h->dbg_flags;
     // resident blocks per CU from the LDS footprint
-    const int per_cu = hfg::rb_lds_bytes(C, rb.nwin, n_all) <= 80 * 1024 ? 2 : 1;
+    const int per_cu = hfg::rb_lds_bytes(C, rb.nwin, n_all) <= hfg::kMaxLdsBytes / 2 ? 2 : 1;
     // a persistent grid of the resident blocks (each window's x load overlaps the previous
     // window's MRF round trip; launch_resblock_bf16x3 runs it where a persistent variant is
     // built, C = 64 with the 512-column window).  RB_PERSIST: 0 off, 1 one block per CU

@@ -11,6 +11,7 @@
 #include <tuple>
 
 #include "handle.h"
+#include "mel_kernels.h"
 
 using namespace hfg_host;
 using hfg::kTiles;
@@ -669,6 +670,32 @@ int hfg_debug_packed_resblock(hfg_handle* h, int stage, int j, float* out, size_
 
 int hfg_debug_thin_window(int C, int mfma) {
   return mfma ? hfg::thin_mfma_window(C) : hfg::thin_window(C);
+}
+
+// What each launcher passes as dynamic LDS (the total of its kernel's layout, lds_layout.h),
+// by the same functions the launchers call.
+int64_t hfg_debug_lds_bytes(const char* family, const int* a, int n) {
+  using namespace hfg;
+  if (!family || !a) return -1;
+  const std::string f = family;
+  if (f == "conv_bf16x3" && n == 4)
+    return a[0] >= 1 && a[0] < kBf16x3Tiles_n && bf16x3_supported(a[1], a[2])
+               ? (int64_t)bf16x3_lds_bytes(a[0], a[1], a[2], a[3] != 0) : -1;
+  if (f == "ups_bf16x3" && n == 1)
+    return a[0] >= 0 && a[0] < kUpsCfgs_n ? (int64_t)ups_lds_bytes(a[0]) : -1;
+  if (f == "resblock_bf16x3" && n == 3)
+    return a[2] >= 1 && a[2] <= kRbMaxConv ? (int64_t)rb_lds_bytes(a[0], a[1], a[2]) : -1;
+  if (f == "mrf_thin" && n == 1) return thin_window(a[0]) ? (int64_t)thin_lds_bytes(a[0]) : -1;
+  if (f == "mrf_thin_mfma" && n == 1)
+    return thin_mfma_window(a[0]) ? (int64_t)thin_mfma_lds_bytes(a[0]) : -1;
+  if (f == "conv1d_mfma_f32" && n == 3)
+    return a[0] >= 0 && a[0] < TILE_COUNT && fp32_conv_supported(a[0], a[1], a[2])
+               ? (int64_t)fp32_conv_lds_bytes(a[0], a[1], a[2]) : -1;
+  if (f == "conv_post" && n == 1) return a[0] >= 1 ? (int64_t)conv_post_lds_bytes(a[0]) : -1;
+  if (f == "logmel_fft" && n == 4)
+    return a[0] >= 16 && !(a[0] & (a[0] - 1)) && a[1] >= 1 && a[2] >= 1 && a[3] >= 1
+               ? (int64_t)logmel_fft_lds_bytes(a[0], a[1], a[3], a[2]) : -1;
+  return -1;
 }
 
 // JSON description of everything the launch code reads from the plan (layers, whole-ResBlock

@@ -102,6 +102,7 @@ constexpr TileCfg kTiles[TILE_COUNT] = {
 
 // the fp32 kernel of `tile` handles kt taps at dilation dil (staging registers, LDS)
 bool fp32_conv_supported(int tile, int kt, int dil);
+size_t fp32_conv_lds_bytes(int tile, int kt, int dil);  // dynamic LDS of that launch
 
 inline TileId tile_for_rows(int M) {
   if (M >= 128) return TILE_M128;
@@ -129,7 +130,8 @@ constexpr int kMaxDil = 16;
 constexpr int halo_max(int dkt) { return dkt == 0 ? 192 : (dkt - 1) * kMaxDil; }
 
 // ---- split-precision bf16x3 conv (conv_bf16x3.hip) ----
-// WD = depth of the weight-slab ring (chunks in flight: WD - 1).
+// WD = weight slabs in LDS: 2 on every live tile (chunk c + 1 lands while chunk c is
+// multiplied; the kernel asserts it).  The LDS carve-up: conv_bf16x3_lds, lds_layout.h.
 struct Bf16x3Cfg {
   int WAVES_M, WAVES_N, WM, WN, TPC, WD;
   int AREG;  // 1: A fragments loaded from global straight into registers (no LDS ring)
@@ -169,23 +171,9 @@ constexpr int kBf16x3Ck = 16;  // channels per chunk (one MFMA k-step per tap)
 // largest (KT-1)*dil window halo of the bf16x3 layer kernel (sizes its staging
 // registers: 3 tasks per thread for the 256-column tiles); wider layers run on the fp32 path
 constexpr int kBf16x3MaxHalo = 128;
-// rows of one staged input plane on the AREG tile: one per staging task (XQ * NT / 2),
-// as conv1d_bf16x3 computes XQ from the largest window of the instantiation
-constexpr int bf16x3_areg_rows(int kt, const Bf16x3Cfg& t) {
-  const int halo = (kt - 1) * kMaxDil < kBf16x3MaxHalo ? (kt - 1) * kMaxDil : kBf16x3MaxHalo;
-  const int xw_max = t.NTILE() + halo;
-  const int nt = t.threads();
-  return (2 * xw_max + nt - 1) / nt * nt / 2;
-}
-// AREG tile: byte offset of the m-tile's bias copy in LDS (read by the LDS-staged epilogue:
-// no global load between its stores) = past both the input planes and the epilogue staging
-constexpr int bf16x3_areg_bias_off(int kt, const Bf16x3Cfg& t) {
-  const int xbytes = 2 * 4 * (bf16x3_areg_rows(kt, t) * 16 + 64);
-  const int stage = t.threads() / 64 * 32 * (32 * t.WN + 8) * 4;
-  return ((xbytes > stage ? xbytes : stage) + 15) & ~15;
-}
 inline int bf16x3_tile_for_rows(int M) { return M >= 128 ? 3 : (M >= 64 ? 1 : (M >= 32 ? 2 : -1)); }
-size_t bf16x3_lds_bytes(int tile, int kt, int dil);
+// dynamic LDS of a launch (lds_layout.h); epi_lds: with the LDS-staged epilogue
+size_t bf16x3_lds_bytes(int tile, int kt, int dil, bool epi_lds);
 // the bf16x3 layer kernel handles kt taps at dilation dil (else the fp32 kernel runs)
 inline bool bf16x3_supported(int kt, int dil) {
   return dil >= 1 && dil <= kMaxDil && kt >= 1 && kt <= 16 && (kt - 1) * dil <= kBf16x3MaxHalo;
@@ -351,10 +339,7 @@ hipError_t launch_conv(TileId tile, int kt, bool ups, const ConvParams& p, int n
                        int m_tiles, int batch, hipStream_t stream, const char** name);
 
 // conv_post + tanh: input rows staged in LDS kConvPostCB channels at a time
-constexpr int kConvPostCB = 32;
-inline size_t conv_post_lds_bytes(int C) {
-  return sizeof(float) * ((size_t)((C * 7 + 3) & ~3) + (size_t)(C < kConvPostCB ? C : kConvPostCB) * (256 + 6));
-}
+constexpr int kConvPostCB = 32;  // (conv_post_lds_bytes: lds_layout.h)
 // conv_post + tanh: wav[b][t] = tanh(bias + sum_{c,j} w[c][j] * lrelu(x[b][c][t+j-3], slope))
 // for t < lens[b] (lens null = L); 0 beyond.  slope: kLReluSlope for the reference, 0.01 for
 // the public release's Generator.  quad: the 4-samples-per-thread kernel
@@ -401,3 +386,5 @@ hipError_t launch_stage_lengths(const int32_t* lens, int B, const StageLenParams
                                 int32_t* out, hipStream_t stream);
 
 }  // namespace hfg
+
+#include "lds_layout.h"

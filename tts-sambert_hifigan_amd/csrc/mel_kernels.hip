@@ -128,11 +128,11 @@ logmel_fft(const float* __restrict__ wav, int64_t n_samp, int n_fft, int hop, in
            int log_mode, float ln_base, float* __restrict__ mel) {
   extern __shared__ __attribute__((aligned(16))) char lds_m[];
   const int N2 = n_fft / 2;
-  const int fpb = 4 * fpw;
-  const int span = (fpb - 1) * hop + n_fft;
+  const int fpb = mel_fft_fpb(fpw);      // (the LDS terms: lds_layout.h)
+  const int span = mel_fft_span(fpb, hop, n_fft);
   cd* const bufs = reinterpret_cast<cd*>(lds_m);                        // [4 waves][2][N2]
-  float* const sig = reinterpret_cast<float*>(lds_m + sizeof(cd) * 8 * N2);  // [span]
-  float* const mel_s = sig + ((span + 3) & ~3);                         // [n_mels][fpb]
+  float* const sig = reinterpret_cast<float*>(lds_m + mel_fft_sig_off(N2));  // [span]
+  float* const mel_s = sig + mel_fft_mel_idx(span);                     // [n_mels][fpb]
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * fpb;
   const int lane = threadIdx.x & 63;
@@ -210,11 +210,9 @@ logmel_fft(const float* __restrict__ wav, int64_t n_samp, int n_fft, int hop, in
   }
 }
 
+static_assert(sizeof(cd) == 2 * sizeof(double), "mel_fft_lds sizes the FFT buffers");
 size_t logmel_fft_lds_bytes(int n_fft, int hop, int fpw, int n_mels) {
-  const int fpb = 4 * fpw;
-  const size_t span = (size_t)(fpb - 1) * hop + n_fft;
-  return sizeof(cd) * 8 * (size_t)(n_fft / 2) + sizeof(float) * ((span + 3) & ~(size_t)3) +
-         sizeof(float) * (size_t)n_mels * fpb;
+  return mel_fft_lds_total(n_fft, hop, fpw, n_mels);
 }
 
 hipError_t launch_logmel_fft(const float* wav, int64_t B, int64_t n_samp, int n_fft, int hop,

@@ -51,7 +51,9 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
   constexpr int NP = NCOL / 2;            // column pairs per thread
   constexpr int NWIN = NT * NCOL;
   constexpr int MARG = kThinMarg;
-  constexpr int RS = NWIN + 2 * MARG;     // LDS row stride (floats)
+  constexpr ThinLds LY = thin_lds(C, NWIN);  // lds_layout.h
+  static_assert(LY.total <= (int)kMaxLdsBytes, "LDS");
+  constexpr int RS = LY.rs;               // LDS row stride (floats)
   constexpr int CG = C < 2 ? C : 2;       // input channels per scalar-load group
   extern __shared__ __attribute__((aligned(16))) float op[];
 
@@ -227,7 +229,7 @@ int thin_window(int C) {
 
 size_t thin_lds_bytes(int C) {
   EntryThin* e = find_thin(C);
-  return e ? sizeof(float) * (size_t)C * (e->nt * e->ncol + 2 * kThinMarg) : 0;
+  return e ? (size_t)thin_lds(C, e->nt * e->ncol).total : 0;
 }
 
 hipError_t launch_mrf_thin(int C, const ThinParams& p, int batch, hipStream_t stream,

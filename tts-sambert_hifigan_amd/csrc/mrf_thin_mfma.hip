@@ -51,13 +51,14 @@ mrf_thin_mfma(const ThinParams p) {
   constexpr int NCT = kThinMfmaTiles;       // 16-column tiles per wave
   constexpr int NWIN = NW * NCT * 16;
   constexpr int MARG = kThinMarg;
-  constexpr int ROWS = NWIN + 2 * MARG;
-  constexpr int RB = 2 * C;                 // bytes per operand row (one plane)
-  constexpr int PS = ROWS * RB;             // bytes per plane
+  constexpr ThinMfmaLds LY = thin_mfma_lds(C, NWIN);  // lds_layout.h
+  static_assert(LY.total <= (int)kMaxLdsBytes, "LDS");
+  constexpr int RB = LY.rb;                 // bytes per operand row (one plane)
+  constexpr int PS = LY.ps;                 // bytes per plane
   constexpr int TPS = 32 / C;               // taps per k-step
   extern __shared__ __attribute__((aligned(16))) char lds[];
   // f16x3: per-wave max |next operand|, after the operand buffers
-  float* const amax_s = reinterpret_cast<float*>(lds + kThinMfmaBufs * 2 * PS);
+  float* const amax_s = reinterpret_cast<float*>(lds + LY.amax_off);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -290,8 +291,7 @@ EntryThinMfma* find_thin_mfma(int C, int fmt = 0, int np = 3) {
 int thin_mfma_window(int C) { return find_thin_mfma(C) ? 4 * kThinMfmaTiles * 16 : 0; }
 
 size_t thin_mfma_lds_bytes(int C) {
-  // operand planes + the f16x3 per-wave maxima
-  return (size_t)kThinMfmaBufs * 2 * (4 * kThinMfmaTiles * 16 + 2 * kThinMarg) * 2 * C + 16;
+  return (size_t)thin_mfma_lds(C, 4 * kThinMfmaTiles * 16).total;
 }
 
 hipError_t launch_mrf_thin_mfma(int C, int fmt, int np, const ThinParams& p, int batch,

@@ -30,12 +30,12 @@ release_mel_fft(const float* __restrict__ wav, int64_t n_samp, const int32_t* __
                 float pad_val, float* __restrict__ mel, int32_t* __restrict__ frame_lens) {
   extern __shared__ __attribute__((aligned(16))) char lds_r[];
   const int N2 = n_fft / 2;
-  const int fpb = 4 * fpw;
-  const int span = (fpb - 1) * hop + n_fft;
+  const int fpb = mel_fft_fpb(fpw);      // (the LDS terms: lds_layout.h)
+  const int span = mel_fft_span(fpb, hop, n_fft);
   const int pad = (n_fft - hop) / 2;
   cd* const bufs = reinterpret_cast<cd*>(lds_r);                        // [4 waves][2][N2]
-  float* const sig = reinterpret_cast<float*>(lds_r + sizeof(cd) * 8 * N2);  // [span]
-  float* const mel_s = sig + ((span + 3) & ~3);                         // [n_mels][fpb]
+  float* const sig = reinterpret_cast<float*>(lds_r + mel_fft_sig_off(N2));  // [span]
+  float* const mel_s = sig + mel_fft_mel_idx(span);                     // [n_mels][fpb]
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * fpb;
   const int lane = threadIdx.x & 63;

@@ -71,7 +71,7 @@ __device__ __forceinline__ void conv_post_tail(const RbParams& p, const floatx16
                                                const bool (&ok)[WN], char* lds, int b, int len_b,
                                                int t0, int tid, int cbase, int half, int col) {
   constexpr int C = 32, KP = 7;
-  constexpr int S = NWIN + 8;  // row stride (floats): the two lane halves' rows, 4 apart, 32 banks apart
+  constexpr int S = rb_lds(C, NWIN).post_row;  // row stride (floats)
   typedef float f4 __attribute__((ext_vector_type(4)));
   float* const s = reinterpret_cast<float*>(lds);
   const int sh = (4 - (p.halo & 3)) & 3;  // staged column = window column + sh: 16-B aligned quads
@@ -194,11 +194,7 @@ bool rb_supported(int C, int kt, int nwin, int wm) {
   return find_rb(C, nwin, wm, kt, 3, 0) != nullptr;
 }
 
-size_t rb_lds_bytes(int C, int nwin, int n_conv) {
-  const size_t rows = (size_t)nwin + 2 * rb_marg(C, nwin);
-  // operand planes, biases, the per-wave maxima of f16x3 (<= 16 waves)
-  return (size_t)C * rows * 4 + sizeof(float) * ((size_t)n_conv * C + 16);
-}
+size_t rb_lds_bytes(int C, int nwin, int n_conv) { return rb_lds(C, nwin).total(n_conv); }
 
 namespace {
 // What both ResBlock launchers share once the instance is chosen: the window, halo and

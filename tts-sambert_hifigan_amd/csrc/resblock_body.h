@@ -38,18 +38,20 @@ resblock_bf16x3(const RbParams p) {
   // columns: the first conv's operand fills its radius of them from x (write_margins), later
   // operands leave them stale (their contents only reach garbage columns)
   constexpr int MARG = rb_marg(C, NWIN);
-  constexpr int ROWS = NWIN + 2 * MARG;
-  constexpr int PS = ROWS * 16;            // bytes per plane: [row][8 bf16]
-  constexpr int HPS = 2 * PS;              // half-group (slots 0-7 | 8-15): hi, lo planes
-  constexpr int GS = 2 * HPS;              // 16-channel group
+  constexpr RbLds LY = rb_lds(C, NWIN);    // lds_layout.h
+  constexpr int ROWS = LY.rows;
+  constexpr int PS = LY.ps;                // bytes per plane: [row][8 bf16]
+  constexpr int HPS = LY.hps;              // half-group (slots 0-7 | 8-15): hi, lo planes
+  constexpr int GS = LY.gs;                // 16-channel group
   constexpr int ASTEP = 2 * 64 * 16;       // bytes per k-step of one wave row-block (hi, lo)
-  static_assert(C != 32 || (WM == 1 && 32 * (NWIN + 8) * 4 <= NG * GS),
+  static_assert(LY.bias_off <= (int)kMaxLdsBytes, "operand planes");
+  static_assert(C != 32 || (WM == 1 && 32 * LY.post_row * 4 <= LY.bias_off),
                 "conv_post staging fits the operand planes");
 
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  float* const bias_s = reinterpret_cast<float*>(lds + NG * GS);
+  float* const bias_s = reinterpret_cast<float*>(lds + LY.bias_off);
   // f16x3: per-wave max |next operand| (NW floats after the biases)
-  float* const amax_s = bias_s + p.n_conv * C;
+  float* const amax_s = bias_s + p.n_conv * LY.bias_conv;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -187,7 +189,7 @@ resblock_bf16x3(const RbParams p) {
   // range (C * L floats) turns the columns outside it into zeros; columns outside [0, len)
   // are masked as in the register path. ----
   constexpr int XD_N = C * ROWS / 64;  // 64-dword pieces (ROWS % 4 == 0: C * ROWS % 64 == 0)
-  static_assert(C * ROWS % 64 == 0 && C * ROWS * 4 == NG * GS, "x copy fills the operand planes");
+  static_assert(C * ROWS % 64 == 0 && C * ROWS * 4 == LY.bias_off, "x copy fills the operand planes");
   constexpr int XD_T = (XD_N + NW - 1) / NW;
   auto dma_x = [&](int wsx, int bi) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(

@@ -31,8 +31,6 @@
 //     for the three tap offsets -1, 0, +1, and staging writes within their transfer cycles).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include <cstdio>
 
 #include "bf16x3_common.h"
@@ -50,9 +48,6 @@
 
 namespace hfg {
 
-namespace {
-}  // namespace
-
 // occupancy: the small tile (2 x 32 x 32 accumulators per class) fits 168 VGPRs, 3 waves per
 // SIMD; its launches (the thin last upsampler) are bound by HBM latency, not the matrix pipe
 template <int WAVES_M, int WAVES_N, int WM, int WN>
@@ -64,14 +59,16 @@ ups_bf16x3(const UpsParams p) {
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int MT = 32 * WM * WAVES_M;      // rows per class and m-tile
   constexpr int NTILE = 32 * WN * WAVES_N;   // frames per block
-  constexpr int XR = NTILE + 8;              // staged frames: [m0 - 4, m0 + NTILE + 4)
+  constexpr UpsLds LY = ups_lds(UpsCfg{WAVES_M, WAVES_N, WM, WN});  // lds_layout.h
+  static_assert(LY.total <= (int)kMaxLdsBytes, "LDS");
+  constexpr int XR = LY.xr;                  // staged frames: [m0 - 4, m0 + NTILE + 4)
   constexpr int NQ = XR / 4;                 // frame quads
   constexpr int NTASK = 2 * NQ;              // (quad, 8-channel half) staging tasks
   constexpr int TPW = (NTASK + NW - 1) / NW; // tasks per wave (one per lane)
   static_assert(TPW <= 64, "one staging task per lane");
-  constexpr int XPLANE = XR * 32;            // bytes per bf16 plane [frame][16 ch]
-  constexpr int XBUF = 2 * XPLANE;           // hi + lo
-  constexpr int SLAB = 2 * 2 * 2 * WAVES_M * WM * 1024;  // bytes: class x tap x plane x rows
+  constexpr int XPLANE = LY.xplane;          // bytes per bf16 plane [frame][16 ch]
+  constexpr int XBUF = LY.xbuf;              // hi + lo
+  constexpr int SLAB = LY.slab;              // bytes: class x tap x plane x rows
   constexpr int PW = SLAB / 1024 / NW;       // LDS-DMA pieces per thread per slab
   static_assert(PW * 1024 * NW == SLAB, "slab must split evenly over the waves");
 
@@ -86,7 +83,7 @@ ups_bf16x3(const UpsParams p) {
   };
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* const Abuf = lds;                    // 2 slabs
-  char* const Xbuf = lds + 2 * SLAB;         // 2 x (hi, lo) planes
+  char* const Xbuf = lds + LY.x_off;         // 2 x (hi, lo) planes
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -395,12 +392,7 @@ EntryUps g_entriesUps[] = {HFGUPS_ENTRY(0, 3, 0), HFGUPS_ENTRY(1, 3, 0), HFGUPS_
 
 }  // namespace
 
-size_t ups_lds_bytes(int cfg) {
-  const UpsCfg& t = kUpsCfgs[cfg];
-  const size_t slab = (size_t)2 * 2 * 2 * t.WAVES_M * t.WM * 1024;
-  const size_t xr = (size_t)t.NTILE() + 8;
-  return 2 * slab + 2 * 2 * xr * 32;
-}
+size_t ups_lds_bytes(int cfg) { return (size_t)ups_lds(kUpsCfgs[cfg]).total; }
 
 hipError_t launch_ups_bf16x3(int cfg, int fmt, int np, const UpsParams& p, hipStream_t stream,
                              const char** name) {
