@@ -48,6 +48,33 @@ def conv_transpose1d(x, w, b, stride, pad):
     return y[:, :, pad: pad + lout] + b[None, :, None]
 
 
+def resblock_forward(f, pre, x, kr, dils, resblock="1"):
+    """One ResBlock / ResBlock2 with the parameters ``pre``.convs* of ``f`` on x [B, C, L]:
+    per dilation x = x + conv2(lrelu(conv1(lrelu(x)))), ResBlock2 x = x + conv(lrelu(x))."""
+    xr = np.asarray(x, np.float64)
+    for m, d in enumerate(dils):
+        if str(resblock) == "2":
+            w, b = f[f"{pre}.convs.{m}.weight"], f[f"{pre}.convs.{m}.bias"]
+            xt = conv1d(lrelu(xr), np.asarray(w, np.float64), np.asarray(b, np.float64),
+                        get_padding(kr, d), d)
+        else:
+            xt = conv1d(lrelu(xr), np.asarray(f[f"{pre}.convs1.{m}.weight"], np.float64),
+                        np.asarray(f[f"{pre}.convs1.{m}.bias"], np.float64), get_padding(kr, d), d)
+            xt = conv1d(lrelu(xt), np.asarray(f[f"{pre}.convs2.{m}.weight"], np.float64),
+                        np.asarray(f[f"{pre}.convs2.{m}.bias"], np.float64), get_padding(kr, 1), 1)
+        xr = xr + xt
+    return xr
+
+
+def mrf_forward(f, pre, x, kernels, dilations, resblock="1"):
+    """MRF (models/hifigan.py:116-131): the mean of its blocks ``pre``resblocks.j on x;
+    ``pre`` is "" for a standalone MRF, "mrfs.i." inside a Generator."""
+    acc = 0.0
+    for j, (kr, dils) in enumerate(zip(kernels, dilations)):
+        acc = acc + resblock_forward(f, f"{pre}resblocks.{j}", x, kr, dils, resblock)
+    return acc / len(kernels)
+
+
 def generator_forward(sd, cfg: GenConfig, mel, tap=None):
     """float64 forward; ``tap(name, array)`` sees conv_pre / ups.i / mrfs.i like
     oracle.hifigan_torch.generator_forward."""

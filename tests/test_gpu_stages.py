@@ -178,7 +178,10 @@ def test_bf16x3_scale_limits(pkg, golden_index):
 def test_resblock_and_mrf_forward_standalone(pkg, precision, preset, stage):
     """gen.mrfs[i](x) and gen.mrfs[i].resblocks[j](x) on their own (models/hifigan.py:
     72-86, 116-131) against the oracle's ResBlock / MRF restatement, at 1e-4 scaled
-    by the tensor's magnitude; the MRF equals the mean of its ResBlocks."""
+    by the tensor's magnitude; the MRF equals the mean of its ResBlocks.  Seam and end
+    correctness is what test_gpu_seams.py establishes: this 1e-4 random-data bar cannot (a
+    halo one column short moves a default-init k = 7 / 11 block by about 4e-5 / 1e-5, evidence line
+    of test_seams_host.py::test_default_scale_moves_are_recorded)."""
     import torch.nn.functional as F
     from oracle import config as C
     from oracle.config import get_padding
