@@ -316,4 +316,10 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
  * ------------------------------------------------------------------------- */
 #include "hifigan_hip_relmel.h"
 
+/* ---------------------------------------------------------------------------
+ * The release's PCM boundary (int16 in, peak normalisation, int16 out) with
+ * per-item lengths: the hfg_pcm section, in a header of its own.
+ * ------------------------------------------------------------------------- */
+#include "hifigan_hip_pcm.h"
+
 #endif /* HIFIGAN_HIP_H */

@@ -10,7 +10,8 @@ from .hifigan import (HiFiGAN, HiFiGANGenerator, MRF, ResBlock, ResBlock2,  # no
 from ._lib import (HipExtensionMissing, HfgError, Handle, load_library, make_config,  # noqa: F401
                    LIB_PATH, check_provenance, schedule_override, schedule_clear,
                    schedule_overrides)
+from . import pcm  # noqa: F401  (the release's PCM boundary: pcm.peak / to_float / to_pcm16)
 
 __all__ = ["HiFiGAN", "HiFiGANGenerator", "MRF", "ResBlock", "ResBlock2", "get_padding", "Handle",
            "HipExtensionMissing", "HfgError", "load_library", "make_config", "LIB_PATH", "check_provenance",
-           "schedule_override", "schedule_clear", "schedule_overrides"]
+           "schedule_override", "schedule_clear", "schedule_overrides", "pcm"]

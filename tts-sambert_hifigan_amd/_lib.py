@@ -244,6 +244,20 @@ RELMEL_SIGNATURES = {
 }
 
 
+PCM_DTYPES = {"int16": 0, "float32": 1}     # HFG_PCM_S16 / HFG_PCM_F32
+PCM_ROUNDINGS = {"trunc": 0, "nearest": 1}  # HFG_PCM_TRUNC / HFG_PCM_NEAREST
+
+# every symbol declared in include/hifigan_hip_pcm.h (the release's PCM boundary)
+PCM_SIGNATURES = {
+    "hfg_pcm_peak": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hfg_pcm_to_float": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_double,
+                                 c_void_p, c_void_p]),
+    "hfg_pcm_offsets": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "hfg_pcm_from_float": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+}
+
+
 def load_library(path: str = LIB_PATH):
     """Open libhifigan_hip.so (cached).  Raises HipExtensionMissing if absent."""
     global _lib
@@ -258,7 +272,7 @@ def load_library(path: str = LIB_PATH):
     # opts in for a same-box A/B against a previous commit's build (HFG_ALLOW_OLD_LIB=1)
     allow_old = os.environ.get("HFG_ALLOW_OLD_LIB") == "1"
     missing = []
-    for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES, **PCM_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             missing.append(name)

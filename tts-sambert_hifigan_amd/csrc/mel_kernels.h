@@ -47,4 +47,24 @@ hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,
                            const float* kern, int n_phases, int stride, int klen, int width,
                            float* y, hipStream_t stream);
 
+// The release's PCM boundary (pcm.hip), rows [B][n] of int16 (s16) or float32, B <= 65535.
+// lens (device int32 [B], or null = n) is clamped into [0, n]; samples at or past an item's
+// length are never read.  Plain launches: no dynamic LDS, nothing allocated.
+// peak[b] = max |x| over the item (int16: |s| / 32768); peak must hold zeros on entry.
+hipError_t launch_pcm_peak(const void* wav, bool s16, int64_t B, int64_t n, const int32_t* lens,
+                           float* peak, hipStream_t stream);
+// out[b][i] = s / 32768 (peak null) or (float)((v / d_b) * gain) in float64, d_b = peak[b], or 1
+// where peak[b] is below the input type's smallest normal number; 0 for i >= len_b.
+hipError_t launch_pcm_to_float(const void* wav, bool s16, int64_t B, int64_t n,
+                               const int32_t* lens, const float* peak, double gain, float* out,
+                               hipStream_t stream);
+// offsets[B + 1]: the exclusive prefix sum of the clamped lengths.
+hipError_t launch_pcm_offsets(const int32_t* lens, int64_t B, int64_t n, int64_t* offsets,
+                              hipStream_t stream);
+// sat16(round(x * 32768)), round toward zero or to nearest even, NaN -> 0.  offsets null:
+// out[B][n], 0 for i >= len_b; else only out[offsets[b] + i], i < len_b.
+hipError_t launch_pcm_from_float(const float* wav, int64_t B, int64_t n, const int32_t* lens,
+                                 bool nearest, const int64_t* offsets, int16_t* out,
+                                 hipStream_t stream);
+
 }  // namespace hfg

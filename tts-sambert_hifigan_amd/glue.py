@@ -42,11 +42,8 @@ def vocode_list(gen, mels: Sequence[torch.Tensor]) -> List[torch.Tensor]:
     return [wav[b, 0, :gen.output_length(lens[b])] for b in range(len(mels))]
 
 
-def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor:
-    """Copy-synthesis on the device: wav [B, N] → ``frontend`` (``mel.ReleaseMelSpectrogram``)
-    → ``gen`` → wav [B, 1, (N // hop) * hop].  With ``lengths`` (valid samples per item of a
-    padded batch) the front end's frame counts go to the Generator as a device tensor — no
-    host round trip — so item b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``."""
+def _check_chain(gen, frontend) -> None:
+    """The front end must frame at the Generator's hop and produce its n_mels."""
     import math
     hop = math.prod(int(u) for u in gen._hfg_args[1])
     if frontend.hop_size != hop:
@@ -55,11 +52,38 @@ def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor
     if frontend.num_mels != gen.n_mels:
         raise ValueError(f"front end num_mels {frontend.num_mels} != the Generator's "
                          f"n_mels {gen.n_mels}")
+
+
+def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor:
+    """Copy-synthesis on the device: wav [B, N] → ``frontend`` (``mel.ReleaseMelSpectrogram``)
+    → ``gen`` → wav [B, 1, (N // hop) * hop].  With ``lengths`` (valid samples per item of a
+    padded batch) the front end's frame counts go to the Generator as a device tensor — no
+    host round trip — so item b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``."""
+    _check_chain(gen, frontend)
     with torch.no_grad():
         if lengths is None:
             return gen(frontend(wav))
         mel, frame_lengths = frontend(wav, lengths)
         return gen(mel, lengths=frame_lengths)
+
+
+def resynthesize_pcm(gen, frontend, pcm: torch.Tensor, lengths=None, normalize: bool = False,
+                     gain: float = 0.95, rounding: str = "trunc", packed: bool = False):
+    """The release's ``inference.py`` loop on the device, PCM in → PCM out: pcm [B, N] int16
+    (or float32) → ``pcm.to_float`` (with ``normalize`` the release's peak normalisation times
+    ``gain``) → ``frontend`` → ``gen`` → ``pcm.to_pcm16``: int16 [B, (N // hop) * hop], or with
+    ``packed`` ``(flat int16, offsets int64 [B + 1])``.  With ``lengths`` the output sample
+    lengths are ``frame_lengths * hop``, formed on the device: no length visits the host, item
+    b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``."""
+    from . import pcm as _pcm
+    _check_chain(gen, frontend)
+    wav = _pcm.to_float(pcm, lengths, normalize=normalize, gain=gain)
+    if lengths is None:
+        return _pcm.to_pcm16(resynthesize(gen, frontend, wav), None, rounding, packed)
+    with torch.no_grad():
+        mel, frame_lengths = frontend(wav, lengths)
+        out = gen(mel, lengths=frame_lengths)
+    return _pcm.to_pcm16(out, frame_lengths * frontend.hop_size, rounding, packed)
 
 
 class StreamingVocoder:
