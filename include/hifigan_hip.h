@@ -322,4 +322,11 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
  * ------------------------------------------------------------------------- */
 #include "hifigan_hip_pcm.h"
 
+/* ---------------------------------------------------------------------------
+ * Ragged multi-channel resampling to mono in front of that chain (int16 or
+ * float32 in, per-item lengths in and out): hfg_resample_ragged, in a header
+ * of its own.
+ * ------------------------------------------------------------------------- */
+#include "hifigan_hip_resample.h"
+
 #endif /* HIFIGAN_HIP_H */

@@ -81,12 +81,12 @@ int hfg_forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, floa
                      float* const* taps, int n_taps, void* stream);
 
 /* Schedule overrides for A/B runs and the parity suites (process-wide; read by every
- * later hfg_create / hfg_mrf_create / hfg_mel_create).  The library reads no environment
+ * later hfg_create / hfg_mrf_create / hfg_mel_create / hfg_resample_create).  The library reads no environment
  * variable for its schedule (the HFG_* knobs of rounds 1-5 are only warned about), so a
  * production handle runs the default schedule whatever its process inherits.  Knobs:
  * FUSED_RB 0|1, FUSE_POST 0|1, RB_SPLIT 0|1, SMALL_TILE -1|0|1, RB_CONC -1|0|1,
  * UPS_FRAMES 1|2, SPLIT 1|2, RB_PERSIST 0..2, DEBUG_FLAGS (ablation builds), MEL_DFT 0|1,
- * AREG_TALL 0|1.
+ * AREG_TALL 0|1, RESAMPLE_TABLE 0|1 (hfg_resample_ragged's filter table: phase-major | tap-major).
  * set: HFG_EINVAL for an unknown knob or a value out of range.  clear: one knob, or all
  * with knob == NULL.  get: 1 and *value if the knob is overridden, 0 if not.
  * knob: the name of knob i of the library's table, NULL past its end. */

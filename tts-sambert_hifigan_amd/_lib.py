@@ -258,6 +258,14 @@ PCM_SIGNATURES = {
 }
 
 
+# every symbol declared in include/hifigan_hip_resample.h (ragged multi-channel resampling)
+RESAMPLE_EX_SIGNATURES = {
+    "hfg_resample_ragged": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+}
+RESAMPLE_MAX_CHANNELS = 8   # HFG_RESAMPLE_MAX_CHANNELS
+
+
 def load_library(path: str = LIB_PATH):
     """Open libhifigan_hip.so (cached).  Raises HipExtensionMissing if absent."""
     global _lib
@@ -272,7 +280,8 @@ def load_library(path: str = LIB_PATH):
     # opts in for a same-box A/B against a previous commit's build (HFG_ALLOW_OLD_LIB=1)
     allow_old = os.environ.get("HFG_ALLOW_OLD_LIB") == "1"
     missing = []
-    for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES, **PCM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES, **PCM_SIGNATURES,
+                              **RESAMPLE_EX_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             missing.append(name)

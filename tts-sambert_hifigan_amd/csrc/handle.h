@@ -44,6 +44,7 @@ constexpr SchedKnob kSchedKnobs[] = {
     {"DEBUG_FLAGS", 0, 1 << 30},  // kernel ablation bits (-DHFG_ABLATE=1 builds only)
     {"MEL_DFT", 0, 1},      // mel: the DFT-GEMM path instead of the FFT (mel_capi.cpp)
     {"AREG_TALL", 0, 1},    // 256-row layers on the 256x128 AREG tile (6) instead of tile 5
+    {"RESAMPLE_TABLE", 0, 1},  // hfg_resample_ragged's filter table: 0 phase-major, 1 tap-major
 };
 // the override of `knob` into *v if one is set (else *v is left alone)
 void sched_apply(const char* knob, int* v);

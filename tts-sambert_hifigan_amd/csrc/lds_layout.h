@@ -195,4 +195,15 @@ constexpr size_t mel_fft_lds_total(int n_fft, int hop, int fpw, int n_mels) {
                           (size_t)n_mels * fpb);
 }
 
+// ---- resample_ragged (resample_ragged.hip): [C channels][the input span of a block's 256
+// outputs]; floats.  The 256 outputs cover at most 255 / n_phases + 1 steps of `stride` input
+// samples beyond the first output's klen taps (resample_sinc's span, mel_kernels.hip). ----
+__host__ __device__ constexpr int resample_span(int n_phases, int stride, int klen) {
+  return (255 / n_phases + 1) * stride + klen;   // floats per channel: the channel stride
+}
+constexpr size_t kResampleRaggedMaxLds = 64 * 1024;  // launched without raising the LDS limit
+constexpr size_t resample_ragged_lds_bytes(int64_t C, int n_phases, int stride, int klen) {
+  return sizeof(float) * (size_t)C * (size_t)resample_span(n_phases, stride, klen);
+}
+
 }  // namespace hfg

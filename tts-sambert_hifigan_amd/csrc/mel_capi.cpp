@@ -342,6 +342,10 @@ struct hfg_resample_handle {
   int width, klen;
   int device;
   float* kern = nullptr;      // [new][klen] on the device
+  // hfg_resample_ragged: the same numbers tap-major, [klen][new], uploaded beside kern so the
+  // call allocates nothing, and which of the two its kernel reads (schedule knob RESAMPLE_TABLE)
+  float* kern_t = nullptr;
+  bool tap_major = true;
 };
 
 namespace {
@@ -398,6 +402,14 @@ int hfg_resample_create(int32_t orig_freq, int32_t new_freq, int32_t lpw, float 
   int rc = hfg_resample_kernel(orig_freq, new_freq, lpw, rolloff, nullptr, &width, &np, &klen);
   if (rc) return rc;
   const long long g = gcd_ll(orig_freq, new_freq);
+  // equal rates: torchaudio returns its input and hfg_resample_forward copies; the handle's
+  // table is the identity (one phase, one tap of 1.0f, no pad), which hfg_resample_ragged runs
+  // to convert, average and mask
+  const bool same = orig_freq == new_freq;
+  if (same) {
+    width = 0;
+    klen = 1;
+  }
   if ((long long)np * klen > (1LL << 24))
     return mfail(HFG_EINVAL, "resample kernel [%d][%d] too large (rates %d -> %d)", np, klen,
                  orig_freq, new_freq);
@@ -413,8 +425,16 @@ int hfg_resample_create(int32_t orig_freq, int32_t new_freq, int32_t lpw, float 
   h->klen = klen;
   h->device = device;
   if (device >= 0) {
-    std::vector<float> k((size_t)np * klen);
-    hfg_resample_kernel(orig_freq, new_freq, lpw, rolloff, k.data(), nullptr, nullptr, nullptr);
+    std::vector<float> k((size_t)np * klen), kt((size_t)np * klen);
+    if (same)
+      k[0] = 1.0f;
+    else
+      hfg_resample_kernel(orig_freq, new_freq, lpw, rolloff, k.data(), nullptr, nullptr, nullptr);
+    for (int j = 0; j < np; ++j)
+      for (int t = 0; t < klen; ++t) kt[(size_t)t * np + j] = k[(size_t)j * klen + t];
+    int tm = 1;  // 0: hfg_resample_ragged reads the phase-major table (A/B: time_resample.py)
+    hfg_debug_schedule_get("RESAMPLE_TABLE", &tm);
+    h->tap_major = tm != 0;
     int prev = -1;
     (void)hipGetDevice(&prev);
     if (hipSetDevice(device) != hipSuccess) {
@@ -423,6 +443,9 @@ int hfg_resample_create(int32_t orig_freq, int32_t new_freq, int32_t lpw, float 
     }
     if (hipMalloc(&h->kern, k.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(h->kern, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMalloc(&h->kern_t, kt.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(h->kern_t, kt.data(), kt.size() * sizeof(float), hipMemcpyHostToDevice) !=
             hipSuccess) {
       hfg_resample_destroy(h);
       return mfail(HFG_ENOMEM, "resample kernel upload");
@@ -436,6 +459,7 @@ int hfg_resample_create(int32_t orig_freq, int32_t new_freq, int32_t lpw, float 
 void hfg_resample_destroy(hfg_resample_handle* h) {
   if (!h) return;
   if (h->kern) (void)hipFree(h->kern);
+  if (h->kern_t) (void)hipFree(h->kern_t);
   delete h;
 }
 
@@ -463,6 +487,42 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
     e = hfg::launch_resample(x, B, n, n_out, h->kern, h->new_, h->orig, h->klen, h->width, y, s);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   if (e != hipSuccess) return mfail(HFG_EIO, "resample launch: %s", hipGetErrorString(e));
+  return HFG_OK;
+}
+
+// include/hifigan_hip_resample.h: every argument is checked before any HIP call
+int hfg_resample_ragged(hfg_resample_handle* h, const void* x, int dtype, int64_t B, int64_t C,
+                        int64_t n_samples, const int32_t* lengths, float* y, int32_t* out_lengths,
+                        void* stream) {
+  const char* who = "hfg_resample_ragged";
+  if (!h || !x || !y) return mfail(HFG_EINVAL, "%s: NULL argument", who);
+  if (B < 1 || B > 65535) return mfail(HFG_EINVAL, "%s: B must be in [1, 65535]", who);
+  if (C < 1 || C > HFG_RESAMPLE_MAX_CHANNELS)
+    return mfail(HFG_EINVAL, "%s: C must be in [1, %d]", who, HFG_RESAMPLE_MAX_CHANNELS);
+  if (n_samples < 1) return mfail(HFG_EINVAL, "%s: n_samples must be >= 1", who);
+  if (dtype != HFG_PCM_S16 && dtype != HFG_PCM_F32)
+    return mfail(HFG_EINVAL, "%s: dtype must be HFG_PCM_S16 (0) or HFG_PCM_F32 (1), got %d", who,
+                 dtype);
+  const int64_t n_out = n_samples > INT32_MAX ? -1 : hfg_resample_out_len(h, n_samples);
+  if (n_out < 1 || n_out > INT32_MAX)
+    return mfail(HFG_EINVAL, "%s: n_samples %lld and its output length must not exceed "
+                 "INT32_MAX", who, (long long)n_samples);
+  const size_t lds = hfg::resample_ragged_lds_bytes(C, h->new_, h->orig, h->klen);
+  if (lds > hfg::kResampleRaggedMaxLds)
+    return mfail(HFG_EINVAL, "%s: the input span of %lld channels (%zu bytes) does not fit the "
+                 "%zu-byte LDS tile at this rate ratio", who, (long long)C, lds,
+                 hfg::kResampleRaggedMaxLds);
+  if (h->device < 0) return mfail(HFG_EINVAL, "%s: host-only resample handle", who);
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (prev != h->device && hipSetDevice(h->device) != hipSuccess)
+    return mfail(HFG_ENODEV, "hipSetDevice(%d)", h->device);
+  const hipError_t e = hfg::launch_resample_ragged(
+      x, dtype == HFG_PCM_S16, B, C, n_samples, lengths, n_out,
+      h->tap_major ? h->kern_t : h->kern, h->tap_major, h->new_, h->orig, h->klen, h->width, y,
+      out_lengths, reinterpret_cast<hipStream_t>(stream));
+  if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
+  if (e != hipSuccess) return mfail(HFG_EIO, "%s launch: %s", who, hipGetErrorString(e));
   return HFG_OK;
 }
 

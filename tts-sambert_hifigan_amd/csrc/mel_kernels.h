@@ -47,6 +47,18 @@ hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,
                            const float* kern, int n_phases, int stride, int klen, int width,
                            float* y, hipStream_t stream);
 
+// Ragged multi-channel resampling to mono (resample_ragged.hip): x[B][C][n] int16 (s16) or
+// float32, lens (device int32 [B], or null = n) clamped into [0, n], samples at or past an item's
+// length never read.  y[b][m], m < out_len_b = ceil(n_phases len_b / stride): launch_resample's
+// sum per channel on the item cropped to len_b, then ((ch_0 + ch_1) + ...) / C for C > 1; 0 for
+// out_len_b <= m < n_out; out_lens (device int32 [B], or null) receives out_len_b.  kern:
+// [n_phases][klen], or with tap_major [klen][n_phases].  B <= 65535, n and n_out <= INT32_MAX,
+// C spans within kResampleRaggedMaxLds (lds_layout.h).
+hipError_t launch_resample_ragged(const void* x, bool s16, int64_t B, int64_t C, int64_t n,
+                                  const int32_t* lens, int64_t n_out, const float* kern,
+                                  bool tap_major, int n_phases, int stride, int klen, int width,
+                                  float* y, int32_t* out_lens, hipStream_t stream);
+
 // The release's PCM boundary (pcm.hip), rows [B][n] of int16 (s16) or float32, B <= 65535.
 // lens (device int32 [B], or null = n) is clamped into [0, n]; samples at or past an item's
 // length are never read.  Plain launches: no dynamic LDS, nothing allocated.

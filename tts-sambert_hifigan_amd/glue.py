@@ -67,23 +67,73 @@ def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor
         return gen(mel, lengths=frame_lengths)
 
 
+_RESAMPLERS = {}
+
+
+def _resampler(orig: int, new: int, device):
+    """mel.Resample(orig, new) on `device`, one per (orig, new, device) (as mel._RESAMPLERS)."""
+    from . import mel as _mel
+    device = torch.device(device)
+    key = (int(orig), int(new), device)
+    rs = _RESAMPLERS.get(key)
+    if rs is None:
+        rs = _RESAMPLERS[key] = _mel.Resample(int(orig), int(new), device=device)
+    return rs
+
+
 def resynthesize_pcm(gen, frontend, pcm: torch.Tensor, lengths=None, normalize: bool = False,
-                     gain: float = 0.95, rounding: str = "trunc", packed: bool = False):
+                     gain: float = 0.95, rounding: str = "trunc", packed: bool = False,
+                     sample_rate: Optional[int] = None, out_sample_rate: Optional[int] = None):
     """The release's ``inference.py`` loop on the device, PCM in → PCM out: pcm [B, N] int16
     (or float32) → ``pcm.to_float`` (with ``normalize`` the release's peak normalisation times
     ``gain``) → ``frontend`` → ``gen`` → ``pcm.to_pcm16``: int16 [B, (N // hop) * hop], or with
     ``packed`` ``(flat int16, offsets int64 [B + 1])``.  With ``lengths`` the output sample
     lengths are ``frame_lengths * hop``, formed on the device: no length visits the host, item
-    b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``."""
+    b equals its solo run and is 0 past ``(lengths[b] // hop) * hop``.
+
+    ``sample_rate`` (the rate of ``pcm``) different from ``frontend.sampling_rate``, or a pcm
+    with channels ``[B, C, N]``, puts ``mel.Resample(sample_rate, frontend.sampling_rate)
+    .ragged(pcm, lengths)`` in front: every channel resampled to the model rate on its own
+    length, then the channel mean, one launch; its device lengths feed the rest of the chain,
+    and ``normalize`` takes the peak of that mono signal, the one the mel sees.
+    ``out_sample_rate`` different from the model rate resamples the Generator's output the same
+    way before the quantiser, so item b holds ``ceil(frame_lengths[b] * hop * out / model)``
+    samples.  With neither given and a 2-d pcm the chain is exactly the one above."""
     from . import pcm as _pcm
     _check_chain(gen, frontend)
-    wav = _pcm.to_float(pcm, lengths, normalize=normalize, gain=gain)
-    if lengths is None:
-        return _pcm.to_pcm16(resynthesize(gen, frontend, wav), None, rounding, packed)
+    model_sr = int(frontend.sampling_rate)
+    resample_in = (isinstance(pcm, torch.Tensor) and pcm.dim() == 3) or (
+        sample_rate is not None and int(sample_rate) != model_sr)
+    resample_out = out_sample_rate is not None and int(out_sample_rate) != model_sr
+    if not resample_in and not resample_out:
+        wav = _pcm.to_float(pcm, lengths, normalize=normalize, gain=gain)
+        if lengths is None:
+            return _pcm.to_pcm16(resynthesize(gen, frontend, wav), None, rounding, packed)
+        with torch.no_grad():
+            mel, frame_lengths = frontend(wav, lengths)
+            out = gen(mel, lengths=frame_lengths)
+        return _pcm.to_pcm16(out, frame_lengths * frontend.hop_size, rounding, packed)
+    if resample_in:
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
+            raise RuntimeError("resynthesize_pcm (MI355X) needs a HIP tensor; no CPU fallback")
+        src_sr = model_sr if sample_rate is None else int(sample_rate)
+        wav, lens = _resampler(src_sr, model_sr, pcm.device).ragged(pcm, lengths)
+        if normalize:
+            wav = _pcm.to_float(wav, lens, normalize=True, gain=gain)
+    else:
+        wav = _pcm.to_float(pcm, lengths, normalize=normalize, gain=gain)
+        lens = lengths
     with torch.no_grad():
-        mel, frame_lengths = frontend(wav, lengths)
-        out = gen(mel, lengths=frame_lengths)
-    return _pcm.to_pcm16(out, frame_lengths * frontend.hop_size, rounding, packed)
+        if lens is None:
+            out, out_lens = gen(frontend(wav)), None
+        else:
+            mel, frame_lengths = frontend(wav, lens)
+            out = gen(mel, lengths=frame_lengths)
+            out_lens = frame_lengths * frontend.hop_size
+    if resample_out:
+        out, out_lens = _resampler(model_sr, int(out_sample_rate), out.device).ragged(
+            out[:, 0], out_lens)
+    return _pcm.to_pcm16(out, out_lens, rounding, packed)
 
 
 class StreamingVocoder:

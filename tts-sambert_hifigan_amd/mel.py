@@ -322,7 +322,11 @@ class Resample:
     (resampling_method="sinc_interp_hann", lowpass_filter_width=6, rolloff=0.99) on the
     HIP device: ``[..., time]`` → ``[..., ceil(time * new / orig)]``.  The kernel table
     is torchaudio's ``_get_sinc_resample_kernel`` (float64, stored fp32), built by
-    ``hfg_resample_kernel``; the polyphase convolution runs in ``resample_sinc``."""
+    ``hfg_resample_kernel``; the polyphase convolution runs in ``resample_sinc``.
+    :meth:`ragged` is the batched front of the release chain: padded multi-channel int16 or
+    float32 items, each resampled at its own length and mixed down to mono, in one launch
+    (``resample_ragged``).  Equal rates are accepted: ``__call__`` returns its input,
+    ``ragged`` runs the identity filter."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000,
                  resampling_method: str = "sinc_interp_hann", lowpass_filter_width: int = 6,
@@ -378,6 +382,46 @@ class Resample:
             self.ptr, ctypes.c_void_p(x.data_ptr()), B, n, ctypes.c_void_p(y.data_ptr()),
             ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return y.reshape(shape[:-1] + (y.shape[-1],))
+
+    def ragged(self, wav: torch.Tensor, lengths=None):
+        """A padded batch to mono at the new rate in one launch (``hfg_resample_ragged``):
+        wav ``[B, N]`` or ``[B, C, N]`` (planar channels, C <= 8), int16 or float32, on the HIP
+        device → ``(y float32 [B, out_len(N)], out_lengths int32 [B] on the device)``.  Item b is
+        resampled as if cropped to ``lengths[b]`` (bitwise ``self(wav[b, :lengths[b]])`` for one
+        channel; int16 enters as ``s / 32768``), channels are averaged after resampling
+        (``((r_0 + r_1) + ...) / C`` in float32, the reference's ``torch.mean(dim=0)`` of the
+        resampled channels), ``y[b]`` is 0 from ``out_lengths[b] = ceil(lengths[b] * new / orig)``
+        on, and samples past a length are never read.  ``lengths``: None (every item has N), a
+        sequence of ints or an int tensor ``[B]``; host values are validated, a device tensor is
+        never read back (the kernel clamps it into ``[0, N]``).  Equal rates run the identity
+        filter: ``y`` is the masked mono mix (for one channel ``wav`` itself, −0.0 becoming +0.0),
+        where ``__call__`` returns its input.  There is no CPU fallback."""
+        from .pcm import _lengths
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
+            raise RuntimeError("Resample.ragged (MI355X) needs a HIP tensor; no CPU fallback")
+        if wav.dim() not in (2, 3) or min(wav.shape) < 1:
+            raise RuntimeError(f"Resample.ragged: expected wav [B, N] or [B, C, N] with every "
+                               f"dimension >= 1, got {tuple(wav.shape)}")
+        if wav.dtype not in (torch.int16, torch.float32):
+            raise RuntimeError(f"Resample.ragged: expected torch.int16 or torch.float32, got "
+                               f"{wav.dtype}")
+        B, N = wav.shape[0], wav.shape[-1]
+        C = wav.shape[1] if wav.dim() == 3 else 1
+        if C > _lib.RESAMPLE_MAX_CHANNELS:
+            raise RuntimeError(f"Resample.ragged: at most {_lib.RESAMPLE_MAX_CHANNELS} channels, "
+                               f"got {C}")
+        lens_t = _lengths(lengths, B, N, wav.device)
+        wav = wav.detach().contiguous()
+        y = torch.empty(B, self.out_len(N), device=wav.device, dtype=torch.float32)
+        out_lens = torch.empty(B, device=wav.device, dtype=torch.int32)
+        with torch.cuda.device(wav.device):
+            _check_mel(self.lib, self.lib.hfg_resample_ragged(
+                self.ptr, ctypes.c_void_p(wav.data_ptr()),
+                _lib.PCM_DTYPES["int16" if wav.dtype == torch.int16 else "float32"], B, C, N,
+                ctypes.c_void_p(lens_t.data_ptr()) if lens_t is not None else None,
+                ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out_lens.data_ptr()),
+                ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+        return y, out_lens
 
 
 def load_config(config_path: str = "configs/config.yaml") -> dict:
