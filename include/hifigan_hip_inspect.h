@@ -67,6 +67,7 @@ int hfg_debug_thin_window(int C, int mfma);
  *   "conv1d_mfma_f32"  {tile, taps, dilation}
  *   "conv_post"        {channels}
  *   "logmel_fft"       {n_fft, hop, n_mels, frames per wave}  (also release_mel_fft)
+ *   "stft_power_mfma"  {n_fft, hop}  (-1 where hfg_mel_create refuses the DFT-GEMM pair)
  * -1 for an unknown family, a wrong argument count, or arguments the family has no kernel
  * for. */
 int64_t hfg_debug_lds_bytes(const char* family, const int* args, int n_args);

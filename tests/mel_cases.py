@@ -4,8 +4,8 @@ test_gpu_resample_shapes.py).  Not a test module and not a conftest: plain helpe
 
 What is under test: the reference's extract_mel path on the device away from its one shape
 (1024 / 256 / 1024 / 80 slaney, B = 2) — logmel_fft (n_fft a power of two), stft_power_mfma +
-mel_log (every other n_fft) and resample_sinc, with their launch code in mel_capi.cpp and
-mel.MelSpectrogram / mel.Resample / mel.extract_mel.
+mel_log (every other n_fft) and resample_sinc, with their launch code in mel_capi.cpp /
+resample_capi.cpp and mel.MelSpectrogram / mel.Resample / mel.extract_mel.
 
 No tolerance is introduced here.  The FFT path keeps test_gpu_mel.py's 1e-5 (log10) on every
 band against oracle.mel_torch.log_mel64; the DFT path keeps _check(fft=False)'s 1e-4 (bands

@@ -1,5 +1,5 @@
 """hfg_resample_ragged / mel.Resample.ragged and glue.resynthesize_pcm's resampling on the GPU
-(csrc/resample_ragged.hip), on the cases of tests/ragged_resample_cases.py.
+(csrc/resample.hip), on the cases of tests/ragged_resample_cases.py.
 
 Bars.  One channel: bitwise the existing kernel (mel.Resample.__call__, resample_sinc) on the
 item cropped to its own length: the same fp32 fma chain in the same tap order.  Several channels:

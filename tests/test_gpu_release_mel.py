@@ -1,5 +1,5 @@
 """The public HiFi-GAN release's mel front end on the GPU (mel.ReleaseMelSpectrogram,
-csrc/release_mel.hip release_mel_fft) against the float64-spectrum restatement
+csrc/mel_kernels.hip release_mel_fft) against the float64-spectrum restatement
 tests/release_mel_oracle.py::mel_f64, in natural-log units.
 
 Bar: max |device - mel_f64| <= 1e-6, derived, not measured: outputs lie in [-11.52, ~3.3],

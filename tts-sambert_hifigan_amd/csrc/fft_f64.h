@@ -1,6 +1,6 @@
-// fft_f64.h — float64 Stockham FFT device helpers shared by the one-launch mel kernels
-// (logmel_fft in mel_kernels.hip, release_mel_fft in release_mel.hip): complex doubles in LDS,
-// in-register radix 2 / 4 / 8 butterflies, one wave per transform.  Device code only.
+// fft_f64.h — float64 Stockham FFT device helpers of the one-launch mel kernels' block body
+// (mel_fft_body.h: logmel_fft and release_mel_fft): complex doubles in LDS, in-register
+// radix 2 / 4 / 8 butterflies, one wave per transform.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // handle.h — what the host orchestration units share: the handle and its plan (layers,
 // whole-ResBlock and thin-stage launches, packed-buffer offsets), the error channel, the
-// schedule-knob table and the device guard.
+// schedule-knob table and the device guard (device_guard.h).
 //   plan.cpp     config validation, the plan, shapes and workspace sizing (no HIP runtime call)
 //   pack.cpp     weights -> the kernels' packed operand orders (host)
 //   forward.cpp  the launch schedule, the weight upload
@@ -16,6 +16,7 @@
 
 #include "../../include/hifigan_hip.h"
 #include "../../include/hifigan_hip_inspect.h"
+#include "device_guard.h"
 #include "kernels.h"
 
 namespace hfg_host {
@@ -130,20 +131,6 @@ struct Stage {
   size_t thin_m_off = 0;           // floats into the packed buffer
   size_t thin_m_bytes = 0;
   std::vector<int> thin_m_conv;    // byte offset of each conv inside the stream
-};
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
 };
 
 }  // namespace hfg_host

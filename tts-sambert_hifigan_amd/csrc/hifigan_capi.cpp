@@ -695,6 +695,10 @@ int64_t hfg_debug_lds_bytes(const char* family, const int* a, int n) {
   if (f == "logmel_fft" && n == 4)
     return a[0] >= 16 && !(a[0] & (a[0] - 1)) && a[1] >= 1 && a[2] >= 1 && a[3] >= 1
                ? (int64_t)logmel_fft_lds_bytes(a[0], a[1], a[3], a[2]) : -1;
+  // the DFT-GEMM pair (n_fft, hop): stft_power_mfma's tile where hfg_mel_create admits the pair
+  if (f == "stft_power_mfma" && n == 2)
+    return a[0] >= 1 && a[1] >= 1 && mel_dft_fits(a[0], a[1]) ? (int64_t)stft_lds_bytes(a[0], a[1])
+                                                              : -1;
   return -1;
 }
 

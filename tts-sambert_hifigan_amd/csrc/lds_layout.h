@@ -176,7 +176,34 @@ constexpr size_t conv_post_lds_bytes(int C) {
          ((size_t)conv_post_x_off(C) + (size_t)(C < kConvPostCB ? C : kConvPostCB) * kConvPostXw);
 }
 
-// ---- logmel_fft / release_mel_fft (mel_kernels.hip, release_mel.hip) ----
+// ---- stft_power_mfma / mel_log (mel_kernels.hip): the DFT-GEMM pair; floats ----
+// stft_power_mfma: the reflect-padded samples of a block's kStftFrames frames, stored skewed:
+// sample i at i + i / hop, so the 32 frames a half-wave reads at one k (frame * hop + k) fall in
+// 32 different banks.  mel_log: kMelLogFrames power rows of n_bins.
+constexpr int kStftFrames = 32, kMelLogFrames = 16;
+__host__ __device__ constexpr int stft_span(int hop, int n_fft) {
+  return (kStftFrames - 1) * hop + n_fft;
+}
+__host__ __device__ constexpr int stft_sig_idx(int i, int hop) { return i + i / hop; }
+constexpr size_t stft_lds_bytes(int n_fft, int hop) {
+  const size_t span = (size_t)(kStftFrames - 1) * hop + n_fft;  // stft_span, past int
+  return sizeof(float) * (span + span / hop + 1);
+}
+constexpr size_t mel_log_lds_bytes(int n_bins) {
+  return sizeof(float) * (size_t)kMelLogFrames * n_bins;
+}
+constexpr size_t kMelDftMaxLds = 64 * 1024;  // both launched without raising the LDS limit
+// What hfg_mel_create admits to the pair.  stft_lds_bytes is the size; the second term is the
+// bound handles were created under before (the tile as if skewed once per 32 samples): it
+// refuses spans of 15888 to about 16350 floats that would fit, and stays so that no
+// configuration changes sides (tests/test_mel_lds_host.py).
+constexpr bool mel_dft_fits(int n_fft, int hop) {
+  return stft_lds_bytes(n_fft, hop) <= kMelDftMaxLds &&
+         ((size_t)(kStftFrames - 1) * hop + n_fft) * 4 * 33 / 32 <= kMelDftMaxLds &&
+         mel_log_lds_bytes(n_fft / 2 + 1) <= kMelDftMaxLds;
+}
+
+// ---- logmel_fft / release_mel_fft (mel_kernels.hip, mel_fft_body.h) ----
 // [4 waves x 2 FFT buffers of n_fft/2 complex doubles][the block's sample span, fp32, rounded
 // up to 16 B][n_mels x frames-per-block output tile, fp32]
 __host__ __device__ constexpr int mel_fft_fpb(int fpw) { return 4 * fpw; }  // frames per block
@@ -195,14 +222,14 @@ constexpr size_t mel_fft_lds_total(int n_fft, int hop, int fpw, int n_mels) {
                           (size_t)n_mels * fpb);
 }
 
-// ---- resample_ragged (resample_ragged.hip): [C channels][the input span of a block's 256
-// outputs]; floats.  The 256 outputs cover at most 255 / n_phases + 1 steps of `stride` input
-// samples beyond the first output's klen taps (resample_sinc's span, mel_kernels.hip). ----
+// ---- resample_sinc / resample_ragged (resample.hip): [C channels][the input span of a
+// block's 256 outputs], C = 1 for resample_sinc; floats.  The 256 outputs cover at most
+// 255 / n_phases + 1 steps of `stride` input samples beyond the first output's klen taps. ----
 __host__ __device__ constexpr int resample_span(int n_phases, int stride, int klen) {
   return (255 / n_phases + 1) * stride + klen;   // floats per channel: the channel stride
 }
-constexpr size_t kResampleRaggedMaxLds = 64 * 1024;  // launched without raising the LDS limit
-constexpr size_t resample_ragged_lds_bytes(int64_t C, int n_phases, int stride, int klen) {
+constexpr size_t kResampleMaxLds = 64 * 1024;  // launched without raising the LDS limit
+constexpr size_t resample_lds_bytes(int64_t C, int n_phases, int stride, int klen) {
   return sizeof(float) * (size_t)C * (size_t)resample_span(n_phases, stride, klen);
 }
 

@@ -1,4 +1,5 @@
-// mel_kernels.h — on-device log-mel framing kernels (mel_kernels.hip).
+// mel_kernels.h — launchers of the audio front end's kernels: the log-mel framings
+// (mel_kernels.hip), the resamplers (resample.hip), the PCM boundary (pcm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +29,7 @@ hipError_t launch_logmel_fft(const float* wav, int64_t B, int64_t n_samp, int n_
                              const int* band, const float* bw, int n_mels, float eps,
                              int log_mode, float ln_base, float* mel, hipStream_t stream);
 
-// The public HiFi-GAN release's mel (release_mel.hip), same tables and block shape as
+// The public HiFi-GAN release's mel (release_mel_fft), same tables and block shape as
 // launch_logmel_fft (and its LDS formula): mel[b][m][f] = ln(max(sum_{k in band m} bw[k]
 // sqrt(|X_f[k]|^2 + spec_eps), clip)), frame f = samples [f hop - p, f hop - p + n_fft),
 // p = (n_fft - hop) / 2 (even difference), reflected at 0 and at the item's length; mel rows
@@ -47,13 +48,13 @@ hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,
                            const float* kern, int n_phases, int stride, int klen, int width,
                            float* y, hipStream_t stream);
 
-// Ragged multi-channel resampling to mono (resample_ragged.hip): x[B][C][n] int16 (s16) or
+// Ragged multi-channel resampling to mono (resample_ragged): x[B][C][n] int16 (s16) or
 // float32, lens (device int32 [B], or null = n) clamped into [0, n], samples at or past an item's
 // length never read.  y[b][m], m < out_len_b = ceil(n_phases len_b / stride): launch_resample's
 // sum per channel on the item cropped to len_b, then ((ch_0 + ch_1) + ...) / C for C > 1; 0 for
 // out_len_b <= m < n_out; out_lens (device int32 [B], or null) receives out_len_b.  kern:
 // [n_phases][klen], or with tap_major [klen][n_phases].  B <= 65535, n and n_out <= INT32_MAX,
-// C spans within kResampleRaggedMaxLds (lds_layout.h).
+// C spans within kResampleMaxLds (lds_layout.h).
 hipError_t launch_resample_ragged(const void* x, bool s16, int64_t B, int64_t C, int64_t n,
                                   const int32_t* lens, int64_t n_out, const float* kern,
                                   bool tap_major, int n_phases, int stride, int klen, int width,

@@ -10,15 +10,17 @@
 //   of the same (frame, bin) in two accumulators and writes |X|^2.
 // mel_log: mel[m][f] = log10(sum_k fb[k][m] * P[f][k] + eps), written as
 //   [B][n_mels][frames], the vocoder's input layout.
+// logmel_fft, release_mel_fft: the whole mel of a tile of frames in one launch, FFT-based
+//   (mel_fft_body.h), in the reference's framing and in the HiFi-GAN release's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 
 #include "epilogue.h"
-#include "fft_f64.h"
 #include "kernels.h"
 #include "launch.h"
+#include "mel_fft_body.h"
 #include "mel_kernels.h"
 
 namespace hfg {
@@ -31,22 +33,21 @@ stft_power_mfma(const float* __restrict__ wav, int64_t N, int n_fft, int hop, in
                 int n_frames, const float* __restrict__ tcos, const float* __restrict__ tsin,
                 int bins_pad, float* __restrict__ power) {
   extern __shared__ __attribute__((aligned(16))) float sig[];
-  constexpr int FT = 32;
+  constexpr int FT = kStftFrames;
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * FT;
   const int half_fft = n_fft / 2;
   const float* x = wav + (int64_t)b * N;
   // reflect-padded samples [f0*hop - n_fft/2, (f0+FT-1)*hop + n_fft/2)
-  // stored skewed: sample s at s + s/hop, so the 32 frames a half-wave reads at
-  // one k (addresses frame*hop + k) fall in 32 different LDS banks
-  const int span = (FT - 1) * hop + n_fft;
+  // stored skewed (stft_sig_idx, lds_layout.h)
+  const int span = stft_span(hop, n_fft);
   for (int i = threadIdx.x; i < span; i += blockDim.x) {
     int64_t g = (int64_t)f0 * hop - half_fft + i;
     if (g < 0) g = -g;                       // torch reflect: x[-i] = x[i]
     if (g >= N) g = 2 * (N - 1) - g;         // x[N-1+i] = x[N-1-i]
     float v = 0.f;
     if (g >= 0 && g < N) v = x[g];
-    sig[i + i / hop] = v;
+    sig[stft_sig_idx(i, hop)] = v;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -67,7 +68,7 @@ stft_power_mfma(const float* __restrict__ wav, int64_t N, int n_fft, int hop, in
 #pragma unroll 4
     for (int k = 0; k < n_fft; k += 2) {
       const int s_ = abase + k;
-      const float a = sig[s_ + s_ / hop];
+      const float a = sig[stft_sig_idx(s_, hop)];
       const float bc = cb[(int64_t)k * bins_pad];
       const float bs = sb[(int64_t)k * bins_pad];
       re = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bc, re, 0, 0, 0);
@@ -88,7 +89,7 @@ __global__ void __launch_bounds__(256)
 mel_log(const float* __restrict__ power, int n_frames, int n_bins, const float* __restrict__ fb,
         int n_mels, float eps, int log_mode, float ln_base, float* __restrict__ mel) {
   extern __shared__ __attribute__((aligned(16))) float pw[];
-  constexpr int FT = 16;
+  constexpr int FT = kMelLogFrames;
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * FT;
   const int nf = min(FT, n_frames - f0);
@@ -107,107 +108,41 @@ mel_log(const float* __restrict__ power, int n_frames, int n_bins, const float* 
 }
 
 // ---------------------------------------------------------------------------------------
-// logmel_fft: the whole log-mel of a tile of frames in one launch, FFT-based.
-//
-// Per frame (one wave): z[n] = w[2n] x[2n] + i w[2n+1] x[2n+1] (the window product in fp32,
-// as torch.stft forms it), an N/2-point complex FFT in float64 by mixed-radix Stockham passes
-// (radix 8, then 4 or 2) ping-ponging between two LDS buffers, the real-FFT split
-// X[k] = (Z[k] + Z*[N/2-k]) / 2 - i e^{-2 pi i k / N} (Z[k] - Z*[N/2-k]) / 2 for
-// k = 0..N/2, |X|^2, the slaney / htk mel projection over each band's nonzero bins, + eps,
-// log.  float64 arithmetic makes the spectrum exact to ~1e-15 of the frame energy, so quiet
-// bins (silence beside loud frames) keep their precision; the O(N log N) FFT replaces the
-// O(N^2) DFT GEMM (stft_power_mfma, kept for n_fft that are not a power of two).
-// Block: 4 waves x fpw frames; the block's reflect-padded sample span is staged once in
-// LDS (fp32) and the [n_mels][frames] tile leaves through LDS as frame-contiguous rows.
-// The FFT helpers (cd, dft_r, stockham_pass, wave_sync) are in fft_f64.h, shared with
-// release_mel_fft (release_mel.hip).
+// logmel_fft: torchaudio MelSpectrogram(power=2, center=True) + log, one launch.  The O(N log N)
+// float64 FFT replaces the O(N^2) DFT GEMM (stft_power_mfma, kept for n_fft that are not a
+// power of two).
 __global__ void __launch_bounds__(256)
 logmel_fft(const float* __restrict__ wav, int64_t n_samp, int n_fft, int hop, int n_frames,
            int fpw, const float* __restrict__ window, const cd* __restrict__ tw,
            const int* __restrict__ band, const float* __restrict__ bw, int n_mels, float eps,
            int log_mode, float ln_base, float* __restrict__ mel) {
-  extern __shared__ __attribute__((aligned(16))) char lds_m[];
-  const int N2 = n_fft / 2;
-  const int fpb = mel_fft_fpb(fpw);      // (the LDS terms: lds_layout.h)
-  const int span = mel_fft_span(fpb, hop, n_fft);
-  cd* const bufs = reinterpret_cast<cd*>(lds_m);                        // [4 waves][2][N2]
-  float* const sig = reinterpret_cast<float*>(lds_m + mel_fft_sig_off(N2));  // [span]
-  float* const mel_s = sig + mel_fft_mel_idx(span);                     // [n_mels][fpb]
+  const LogMelFront F{n_fft / 2, n_samp, n_frames, n_frames, eps, ln_base, log_mode};
+  mel_fft_block(F, wav + (int64_t)blockIdx.y * n_samp, n_fft, hop, fpw, window, tw, band, bw,
+                n_mels, mel);
+}
+
+// release_mel_fft: the public HiFi-GAN release's mel front end (meldataset.mel_spectrogram) in
+// one launch per batch: reflect pad of (n_fft - hop) / 2 a side, torch.stft(center=False,
+// periodic Hann), sqrt(re^2 + im^2 + 1e-9), the librosa (Slaney) filterbank,
+// ln(max(mel, 1e-5)); N samples -> N / hop frames.  Ragged batches: a per-item length, indices
+// reflected at 0 and at the item's own length; columns at or past an item's frame count get
+// log(clip), the mel of digital silence.
+__global__ void __launch_bounds__(256)
+release_mel_fft(const float* __restrict__ wav, int64_t n_samp, const int32_t* __restrict__ lens,
+                int n_fft, int hop, int n_cols, int fpw, const float* __restrict__ window,
+                const cd* __restrict__ tw, const int* __restrict__ band,
+                const float* __restrict__ bw, int n_mels, double spec_eps, double clip,
+                float pad_val, float* __restrict__ mel, int32_t* __restrict__ frame_lens) {
   const int b = blockIdx.y;
-  const int f0 = blockIdx.x * fpb;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const float* x = wav + (int64_t)b * n_samp;
-  // reflect-padded samples [f0 hop - N/2, f0 hop - N/2 + span)  (torch reflect: x[-i] = x[i],
-  // x[L-1+i] = x[L-1-i]; the host checks L > N/2)
-  for (int i = threadIdx.x; i < span; i += 256) {
-    int64_t g = (int64_t)f0 * hop - N2 + i;
-    if (g < 0) g = -g;
-    if (g >= n_samp) g = 2 * (n_samp - 1) - g;
-    sig[i] = (g >= 0 && g < n_samp) ? x[g] : 0.f;
-  }
-  __syncthreads();
-  cd* A = bufs + (size_t)wave * 2 * N2;
-  cd* Bf = A + N2;
-  for (int fi = 0; fi < fpw; ++fi) {
-    const int fl = wave * fpw + fi;  // frame within the block
-    if (f0 + fl >= n_frames) break;  // wave-uniform
-    const float* fr = sig + fl * hop;
-    for (int n = lane; n < N2; n += 64) {
-      const float x0 = fr[2 * n] * window[2 * n], x1 = fr[2 * n + 1] * window[2 * n + 1];
-      A[n] = {(double)x0, (double)x1};
-    }
-    wave_sync();
-    cd* src = A;
-    cd* dst = Bf;
-    int Ns = 1, rem = __builtin_ctz(N2);
-    while (rem > 0) {
-      if (rem >= 3) {
-        stockham_pass<8>(src, dst, N2, Ns, tw, lane);
-        Ns *= 8;
-        rem -= 3;
-      } else if (rem == 2) {
-        stockham_pass<4>(src, dst, N2, Ns, tw, lane);
-        Ns *= 4;
-        rem -= 2;
-      } else {
-        stockham_pass<2>(src, dst, N2, Ns, tw, lane);
-        Ns *= 2;
-        rem -= 1;
-      }
-      wave_sync();
-      cd* t = src;
-      src = dst;
-      dst = t;
-    }
-    // real-FFT split and power, k = 0..N2, into the free buffer as doubles
-    double* P = reinterpret_cast<double*>(dst);
-    for (int k = lane; k <= N2; k += 64) {
-      const cd zk = src[k & (N2 - 1)];
-      const cd zm = src[(N2 - k) & (N2 - 1)];
-      const cd zc = {zm.x, -zm.y};
-      const cd s_ = cadd(zk, zc), d_ = csub(zk, zc);
-      const cd wd = cmul(tw[k], d_);                 // e^{-2 pi i k/N} (Z[k] - Z*[N2-k])
-      const double re = 0.5 * (s_.x + wd.y), im = 0.5 * (s_.y - wd.x);  // (s - i wd) / 2
-      P[k] = re * re + im * im;
-    }
-    wave_sync();
-    for (int m = lane; m < n_mels; m += 64) {
-      const int lo = band[3 * m], hi = band[3 * m + 1], off = band[3 * m + 2];
-      double acc = 0.0;
-      for (int k = lo; k < hi; ++k) acc += (double)bw[off + k - lo] * P[k];
-      const double v = acc + (double)eps;
-      const double lv = log_mode == 1 ? log10(v) : (log_mode == 0 ? log(v) : log(v) / (double)ln_base);
-      mel_s[m * fpb + fl] = (float)lv;
-    }
-    wave_sync();
-  }
-  __syncthreads();
-  const int nf = min(fpb, n_frames - f0);
-  for (int i = threadIdx.x; i < n_mels * fpb; i += 256) {
-    const int m = i / fpb, fl = i - m * fpb;
-    if (fl < nf) mel[((int64_t)b * n_mels + m) * n_frames + f0 + fl] = mel_s[m * fpb + fl];
-  }
+  const int pad = (n_fft - hop) / 2;
+  // the item's length, clamped into [0, n_samp]: whatever lens holds, every index the body
+  // forms stays inside the item's n_samp floats
+  int64_t len = n_samp;
+  if (lens) len = min(max((int64_t)lens[b], (int64_t)0), n_samp);
+  const int frames = (len > pad && len >= hop) ? (int)min(len / hop, (int64_t)n_cols) : 0;
+  if (frame_lens && blockIdx.x == 0 && threadIdx.x == 0) frame_lens[b] = frames;
+  const ReleaseMelFront F{pad, len, frames, n_cols, spec_eps, clip, pad_val};
+  mel_fft_block(F, wav + (int64_t)b * n_samp, n_fft, hop, fpw, window, tw, band, bw, n_mels, mel);
 }
 
 static_assert(sizeof(cd) == 2 * sizeof(double), "mel_fft_lds sizes the FFT buffers");
@@ -230,13 +165,32 @@ hipError_t launch_logmel_fft(const float* wav, int64_t B, int64_t n_samp, int n_
                          mel);
 }
 
+hipError_t launch_release_mel_fft(const float* wav, int64_t B, int64_t n_samp,
+                                  const int32_t* lens, int n_fft, int hop, int fpw,
+                                  const float* window, const void* tw, const int* band,
+                                  const float* bw, int n_mels, float spec_eps, float clip,
+                                  float* mel, int32_t* frame_lens, hipStream_t stream) {
+  if (n_fft < 16 || (n_fft & (n_fft - 1)) || fpw < 1 || hop < 1 || hop > n_fft ||
+      ((n_fft - hop) & 1) || B < 1 || B > 65535)
+    return hipErrorInvalidValue;
+  const int64_t n_cols = n_samp / hop;
+  if (n_cols < 1 || n_cols > INT32_MAX) return hipErrorInvalidValue;
+  static auto inst = instance_of(release_mel_fft);
+  auto fmt_name = [](char* s, size_t n) { snprintf(s, n, "release_mel_fft"); };
+  dim3 grid((unsigned)((n_cols + 4 * fpw - 1) / (4 * fpw)), (unsigned)B);
+  return launch_instance(inst, fmt_name, grid, dim3(256),
+                         logmel_fft_lds_bytes(n_fft, hop, fpw, n_mels), stream, nullptr, wav,
+                         n_samp, lens, n_fft, hop, (int)n_cols, fpw, window,
+                         reinterpret_cast<const cd*>(tw), band, bw, n_mels, (double)spec_eps,
+                         (double)clip, (float)log((double)clip), mel, frame_lens);
+}
+
 hipError_t launch_stft_power(const float* wav, int64_t B, int64_t N, int n_fft, int hop,
                              int n_bins, int n_frames, const float* tcos, const float* tsin,
                              int bins_pad, float* power, hipStream_t stream) {
-  const size_t span = (size_t)31 * hop + n_fft;
-  const size_t lds = sizeof(float) * (span + span / hop + 1);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  dim3 grid((n_frames + 31) / 32, (unsigned)B);
+  const size_t lds = stft_lds_bytes(n_fft, hop);
+  if (lds > kMelDftMaxLds) return hipErrorInvalidValue;
+  dim3 grid((n_frames + kStftFrames - 1) / kStftFrames, (unsigned)B);
   stft_power_mfma<<<grid, dim3(256), lds, stream>>>(wav, N, n_fft, hop, n_bins, n_frames, tcos,
                                                     tsin, bins_pad, power);
   return hipGetLastError();
@@ -245,56 +199,11 @@ hipError_t launch_stft_power(const float* wav, int64_t B, int64_t N, int n_fft, 
 hipError_t launch_mel_log(const float* power, int64_t B, int n_frames, int n_bins,
                           const float* fb, int n_mels, float eps, int log_mode, float ln_base,
                           float* mel, hipStream_t stream) {
-  const size_t lds = sizeof(float) * (size_t)16 * n_bins;
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  dim3 grid((n_frames + 15) / 16, (unsigned)B);
+  const size_t lds = mel_log_lds_bytes(n_bins);
+  if (lds > kMelDftMaxLds) return hipErrorInvalidValue;
+  dim3 grid((n_frames + kMelLogFrames - 1) / kMelLogFrames, (unsigned)B);
   mel_log<<<grid, dim3(256), lds, stream>>>(power, n_frames, n_bins, fb, n_mels, eps, log_mode,
                                             ln_base, mel);
-  return hipGetLastError();
-}
-
-// Polyphase sinc resampling (torchaudio _apply_sinc_resample_kernel: conv1d of the padded
-// signal with the [n_phases][klen] kernel at stride `stride`, phases interleaved).  A block
-// owns 256 consecutive outputs; the input span they read (<= 256/n_phases*stride + klen
-// samples) is staged in LDS once, zero outside [0, n), and every output is one dot product
-// of klen taps: an HBM-bound stream (reads ~stride/n_phases inputs per output).
-__global__ void __launch_bounds__(256)
-resample_sinc(const float* __restrict__ x, int64_t n, int64_t n_out,
-              const float* __restrict__ kern, int n_phases, int stride, int klen, int width,
-              float* __restrict__ y) {
-  extern __shared__ float xs[];
-  const int b = blockIdx.y;
-  const int64_t m0 = (int64_t)blockIdx.x * 256;
-  const int64_t q0 = m0 / n_phases;                     // first output frame of the block
-  const int64_t q1 = (min(m0 + 256, n_out) - 1) / n_phases;
-  const int64_t s0 = q0 * stride - width;               // first input sample read
-  const int span = (int)((q1 - q0) * stride + klen);
-  const float* xb = x + (int64_t)b * n;
-  for (int i = threadIdx.x; i < span; i += 256) {
-    const int64_t g = s0 + i;
-    xs[i] = (g >= 0 && g < n) ? xb[g] : 0.f;
-  }
-  __syncthreads();
-  const int64_t m = m0 + threadIdx.x;
-  if (m >= n_out) return;
-  const int64_t q = m / n_phases;
-  const int j = (int)(m - q * n_phases);
-  const float* kr = kern + (int64_t)j * klen;
-  const float* xr = xs + (q - q0) * stride;
-  float acc = 0.f;
-  for (int k = 0; k < klen; ++k) acc = fmaf(xr[k], kr[k], acc);
-  y[(int64_t)b * n_out + m] = acc;
-}
-
-hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,
-                           const float* kern, int n_phases, int stride, int klen, int width,
-                           float* y, hipStream_t stream) {
-  const int64_t span = (int64_t)(255 / n_phases + 1) * stride + klen;
-  const size_t lds = sizeof(float) * (size_t)span;
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  dim3 grid((unsigned)((n_out + 255) / 256), (unsigned)B);
-  resample_sinc<<<grid, dim3(256), lds, stream>>>(x, n, n_out, kern, n_phases, stride, klen,
-                                                  width, y);
   return hipGetLastError();
 }
 

@@ -1,12 +1,14 @@
-// resample_ragged.hip — the resampler in front of the release chain: a padded batch of
-// planar multi-channel items x[B][C][n], int16 or float32, each with its own length, to mono
-// float32 y[B][n_out] at the handle's rate ratio, in one launch (include/hifigan_hip_resample.h).
+// resample.hip — polyphase sinc resampling (torchaudio.transforms.Resample): resample_sinc,
+// rows of one length, and resample_ragged, the resampler in front of the release chain.
+//
+// resample_ragged: a padded batch of planar multi-channel items x[B][C][n], int16 or float32,
+// each with its own length, to mono float32 y[B][n_out] at the handle's rate ratio, in one
+// launch (include/hifigan_hip_resample.h).
 //
 // Per item b: len_b = lens[b] clamped into [0, n] (null lens: n), out_len_b =
 // ceil(n_phases * len_b / stride).  For m < out_len_b every channel c gets resample_sinc's own
-// sum (mel_kernels.hip): one sequential fp32 fmaf chain from 0.f over the klen taps of phase
-// m % n_phases on channel c of the item, zero outside [0, len_b), an int16 sample entering as
-// (float) s / 32768.  C = 1 stores that chain; C > 1 stores ((chain_0 + chain_1) + ...) / (float) C:
+// sum: one sequential fp32 fmaf chain from 0.f over the klen taps of phase m % n_phases on
+// channel c of the item, zero outside [0, len_b), an int16 sample entering as (float) s / 32768.  C = 1 stores that chain; C > 1 stores ((chain_0 + chain_1) + ...) / (float) C:
 // the reference's order, resample every channel, then the mean over channels.  Outputs in
 // [out_len_b, n_out) are 0 and out_lens[b] = out_len_b.  Samples at or past len_b are never
 // read.
@@ -26,6 +28,50 @@
 #include "mel_kernels.h"
 
 namespace hfg {
+
+// Polyphase sinc resampling (torchaudio _apply_sinc_resample_kernel: conv1d of the padded
+// signal with the [n_phases][klen] kernel at stride `stride`, phases interleaved).  A block
+// owns 256 consecutive outputs; the input span they read (<= 256/n_phases*stride + klen
+// samples) is staged in LDS once, zero outside [0, n), and every output is one dot product
+// of klen taps: an HBM-bound stream (reads ~stride/n_phases inputs per output).
+__global__ void __launch_bounds__(256)
+resample_sinc(const float* __restrict__ x, int64_t n, int64_t n_out,
+              const float* __restrict__ kern, int n_phases, int stride, int klen, int width,
+              float* __restrict__ y) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const int64_t m0 = (int64_t)blockIdx.x * 256;
+  const int64_t q0 = m0 / n_phases;                     // first output frame of the block
+  const int64_t q1 = (min(m0 + 256, n_out) - 1) / n_phases;
+  const int64_t s0 = q0 * stride - width;               // first input sample read
+  const int span = (int)((q1 - q0) * stride + klen);
+  const float* xb = x + (int64_t)b * n;
+  for (int i = threadIdx.x; i < span; i += 256) {
+    const int64_t g = s0 + i;
+    xs[i] = (g >= 0 && g < n) ? xb[g] : 0.f;
+  }
+  __syncthreads();
+  const int64_t m = m0 + threadIdx.x;
+  if (m >= n_out) return;
+  const int64_t q = m / n_phases;
+  const int j = (int)(m - q * n_phases);
+  const float* kr = kern + (int64_t)j * klen;
+  const float* xr = xs + (q - q0) * stride;
+  float acc = 0.f;
+  for (int k = 0; k < klen; ++k) acc = fmaf(xr[k], kr[k], acc);
+  y[(int64_t)b * n_out + m] = acc;
+}
+
+hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,
+                           const float* kern, int n_phases, int stride, int klen, int width,
+                           float* y, hipStream_t stream) {
+  const size_t lds = resample_lds_bytes(1, n_phases, stride, klen);
+  if (lds > kResampleMaxLds) return hipErrorInvalidValue;
+  dim3 grid((unsigned)((n_out + 255) / 256), (unsigned)B);
+  resample_sinc<<<grid, dim3(256), lds, stream>>>(x, n, n_out, kern, n_phases, stride, klen,
+                                                  width, y);
+  return hipGetLastError();
+}
 
 __device__ __forceinline__ float rr_sample(int16_t s) { return (float)s / 32768.0f; }
 __device__ __forceinline__ float rr_sample(float x) { return x; }
@@ -119,8 +165,8 @@ hipError_t launch_resample_ragged(const void* x, bool s16, int64_t B, int64_t C,
                                   float* y, int32_t* out_lens, hipStream_t stream) {
   if (B < 1 || B > 65535 || C < 1 || n < 1 || n_out < 1 || n > INT32_MAX || n_out > INT32_MAX)
     return hipErrorInvalidValue;
-  const size_t lds = resample_ragged_lds_bytes(C, n_phases, stride, klen);
-  if (lds > kResampleRaggedMaxLds) return hipErrorInvalidValue;
+  const size_t lds = resample_lds_bytes(C, n_phases, stride, klen);
+  if (lds > kResampleMaxLds) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n_out + 255) / 256), (unsigned)B);
   const int16_t* xi = static_cast<const int16_t*>(x);
   const float* xf = static_cast<const float*>(x);

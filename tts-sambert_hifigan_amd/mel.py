@@ -22,8 +22,6 @@ There is no CPU fallback: a CPU waveform raises.
 from __future__ import annotations
 
 import ctypes
-import os
-import struct
 from pathlib import Path
 from typing import Optional, Tuple, Union
 
@@ -31,12 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frontend import (HandleOwner, check, default_device, float_ptr, lengths as _lengths,
+                        ptr as _ptr, riff_chunks, stream as _stream)
 from .hifigan import _lengths_on
-
-
-def _check_mel(lib, rc):
-    if rc != 0:
-        raise _lib.HfgError(rc, lib.hfg_mel_last_error().decode())
 
 
 def _log_base_code(log_base):
@@ -100,14 +95,13 @@ def stft_window(n_fft: int, win_length: int) -> torch.Tensor:
     return w
 
 
-class MelSpectrogram:
+class MelSpectrogram(HandleOwner):
     """torchaudio.transforms.MelSpectrogram(power=2) + log on the HIP device."""
 
     def __init__(self, sample_rate: int = 22050, n_fft: int = 1024, hop_length: int = 256,
                  win_length: int = 1024, n_mels: int = 80, f_min: float = 0.0,
                  f_max: float = 8000.0, mel_scale: str = "slaney", norm: Optional[str] = "slaney",
                  log_eps: float = 1e-10, log_base=10.0, device=None):
-        self.lib = _lib.load_library()
         c = _lib.HfgMelConfig()
         c.sample_rate, c.n_fft, c.hop_length, c.win_length, c.n_mels = (
             sample_rate, n_fft, hop_length, win_length, n_mels)
@@ -120,18 +114,11 @@ class MelSpectrogram:
         self.hop = hop_length
         self.n_mels = n_mels
         self.sample_rate = sample_rate
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        h = ctypes.c_void_p()
-        _check_mel(self.lib, self.lib.hfg_mel_create(ctypes.byref(c), self.device.index or 0,
-                                                     ctypes.byref(h)))
-        self.ptr = h
+        self._open("hfg_mel_create", "hfg_mel_destroy", ctypes.byref(c), device=device)
         # the reference's float32 window and filterbank (bitwise torch.stft / torchaudio)
         self._window = stft_window(n_fft, win_length).contiguous()
         self._fb = melscale_fbanks(n_fft // 2 + 1, float(f_min), float(f_max), n_mels,
                                    sample_rate, norm, mel_scale).contiguous()
-        fp = ctypes.POINTER(ctypes.c_float)
         if not hasattr(self.lib, "hfg_mel_set_tables"):
             # only an A/B against an older library (HFG_ALLOW_OLD_LIB=1) gets here: its
             # device tables are double-evaluated, not torchaudio's float32 ones
@@ -139,16 +126,8 @@ class MelSpectrogram:
             warnings.warn("libhifigan_hip.so lacks hfg_mel_set_tables: mel tables are "
                           "double-evaluated, not the reference's float32 window / filterbank")
             return
-        _check_mel(self.lib, self.lib.hfg_mel_set_tables(
-            self.ptr, ctypes.cast(self._window.data_ptr(), fp), ctypes.cast(self._fb.data_ptr(), fp)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "ptr", None):
-                self.lib.hfg_mel_destroy(self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
+        check(self.lib, self.lib.hfg_mel_set_tables(self.ptr, float_ptr(self._window),
+                                                    float_ptr(self._fb)))
 
     def filterbank(self) -> torch.Tensor:
         """The [n_fft/2+1, n_mels] filterbank the device uses (torchaudio's, float32)."""
@@ -173,10 +152,8 @@ class MelSpectrogram:
         mel = torch.empty(B, self.n_mels, T, device=wav.device, dtype=torch.float32)
         ws_bytes = int(self.lib.hfg_mel_workspace_bytes(self.ptr, B, N))
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=wav.device)
-        _check_mel(self.lib, self.lib.hfg_mel_forward(
-            self.ptr, ctypes.c_void_p(wav.data_ptr()), B, N, ctypes.c_void_p(mel.data_ptr()),
-            ctypes.c_void_p(ws.data_ptr()), ws_bytes,
-            ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+        check(self.lib, self.lib.hfg_mel_forward(self.ptr, _ptr(wav), B, N, _ptr(mel), _ptr(ws),
+                                                 ws_bytes, _stream(wav.device)))
         return mel
 
 
@@ -209,7 +186,7 @@ def librosa_mel_fn(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: Optional
     return weights.astype(np.float32)
 
 
-class ReleaseMelSpectrogram:
+class ReleaseMelSpectrogram(HandleOwner):
     """The public HiFi-GAN release's ``meldataset.mel_spectrogram`` on the HIP device (the
     mel every released ``generator_v*`` checkpoint expects): reflect pad of
     ``(n_fft - hop_size) / 2`` a side, ``torch.stft(center=False)`` with the periodic Hann
@@ -228,7 +205,6 @@ class ReleaseMelSpectrogram:
     def __init__(self, sampling_rate: int = 22050, n_fft: int = 1024, hop_size: int = 256,
                  win_size: int = 1024, num_mels: int = 80, fmin: float = 0.0,
                  fmax: Optional[float] = 8000.0, device=None):
-        self.lib = _lib.load_library()
         c = _lib.HfgRelmelConfig()
         c.sampling_rate, c.n_fft, c.hop_size, c.win_size, c.num_mels = (
             int(sampling_rate), int(n_fft), int(hop_size), int(win_size), int(num_mels))
@@ -238,30 +214,14 @@ class ReleaseMelSpectrogram:
         self.sampling_rate, self.n_fft, self.hop_size = int(sampling_rate), int(n_fft), int(hop_size)
         self.win_size, self.num_mels = int(win_size), int(num_mels)
         self.pad = (self.n_fft - self.hop_size) // 2
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        h = ctypes.c_void_p()
-        _check_mel(self.lib, self.lib.hfg_relmel_create(ctypes.byref(c), self.device.index or 0,
-                                                        ctypes.byref(h)))
-        self.ptr = h
+        self._open("hfg_relmel_create", "hfg_relmel_destroy", ctypes.byref(c), device=device)
         # the release's float32 window (torch.hann_window, centred by torch.stft) and
         # librosa's filterbank, stored [n_fft/2+1, num_mels] as the kernel reads it
         self._window = stft_window(self.n_fft, self.win_size).contiguous()
         self._fb = torch.from_numpy(np.ascontiguousarray(
             librosa_mel_fn(self.sampling_rate, self.n_fft, self.num_mels, fmin, fmax).T))
-        fp = ctypes.POINTER(ctypes.c_float)
-        _check_mel(self.lib, self.lib.hfg_relmel_set_tables(
-            self.ptr, ctypes.cast(self._window.data_ptr(), fp),
-            ctypes.cast(self._fb.data_ptr(), fp)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "ptr", None):
-                self.lib.hfg_relmel_destroy(self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
+        check(self.lib, self.lib.hfg_relmel_set_tables(self.ptr, float_ptr(self._window),
+                                                       float_ptr(self._fb)))
 
     def filterbank(self) -> torch.Tensor:
         """The [n_fft/2+1, num_mels] filterbank the device uses (librosa's, transposed)."""
@@ -308,16 +268,13 @@ class ReleaseMelSpectrogram:
         frame_lens = (torch.empty(B, device=wav.device, dtype=torch.int32)
                       if lens_t is not None else None)
         with torch.cuda.device(wav.device):
-            _check_mel(self.lib, self.lib.hfg_relmel_forward(
-                self.ptr, ctypes.c_void_p(wav.data_ptr()), B, N,
-                ctypes.c_void_p(lens_t.data_ptr()) if lens_t is not None else None,
-                ctypes.c_void_p(mel.data_ptr()),
-                ctypes.c_void_p(frame_lens.data_ptr()) if frame_lens is not None else None,
-                ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+            check(self.lib, self.lib.hfg_relmel_forward(
+                self.ptr, _ptr(wav), B, N, _ptr(lens_t), _ptr(mel), _ptr(frame_lens),
+                _stream(wav.device)))
         return mel if lens_t is None else (mel, frame_lens)
 
 
-class Resample:
+class Resample(HandleOwner):
     """torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults
     (resampling_method="sinc_interp_hann", lowpass_filter_width=6, rolloff=0.99) on the
     HIP device: ``[..., time]`` → ``[..., ceil(time * new / orig)]``.  The kernel table
@@ -334,36 +291,21 @@ class Resample:
         if resampling_method != "sinc_interp_hann":
             raise NotImplementedError("only sinc_interp_hann (torchaudio's default, the one "
                                       "audio_processing.py:84-87 uses) is implemented")
-        self.lib = _lib.load_library()
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.lowpass_filter_width, self.rolloff = int(lowpass_filter_width), float(rolloff)
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        h = ctypes.c_void_p()
-        _check_mel(self.lib, self.lib.hfg_resample_create(
-            self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff,
-            self.device.index or 0, ctypes.byref(h)))
-        self.ptr = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "ptr", None):
-                self.lib.hfg_resample_destroy(self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
+        self._open("hfg_resample_create", "hfg_resample_destroy", self.orig_freq, self.new_freq,
+                   self.lowpass_filter_width, self.rolloff, device=device)
 
     def kernel(self) -> Tuple[torch.Tensor, int]:
         """(kernel [new/g, 2*width + orig/g], width) — torchaudio's (kernel, width)."""
         w, n, k = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _check_mel(self.lib, self.lib.hfg_resample_kernel(
+        check(self.lib, self.lib.hfg_resample_kernel(
             self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, None,
             ctypes.byref(w), ctypes.byref(n), ctypes.byref(k)))
         out = torch.zeros(n.value, k.value)
-        _check_mel(self.lib, self.lib.hfg_resample_kernel(
+        check(self.lib, self.lib.hfg_resample_kernel(
             self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff,
-            ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float)), None, None, None))
+            float_ptr(out), None, None, None))
         return out, w.value
 
     def out_len(self, n: int) -> int:
@@ -378,9 +320,8 @@ class Resample:
         x = waveform.detach().to(torch.float32).reshape(-1, shape[-1]).contiguous()
         B, n = x.shape
         y = torch.empty(B, self.out_len(n), device=x.device, dtype=torch.float32)
-        _check_mel(self.lib, self.lib.hfg_resample_forward(
-            self.ptr, ctypes.c_void_p(x.data_ptr()), B, n, ctypes.c_void_p(y.data_ptr()),
-            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        check(self.lib, self.lib.hfg_resample_forward(self.ptr, _ptr(x), B, n, _ptr(y),
+                                                      _stream(x.device)))
         return y.reshape(shape[:-1] + (y.shape[-1],))
 
     def ragged(self, wav: torch.Tensor, lengths=None):
@@ -396,7 +337,6 @@ class Resample:
         never read back (the kernel clamps it into ``[0, N]``).  Equal rates run the identity
         filter: ``y`` is the masked mono mix (for one channel ``wav`` itself, −0.0 becoming +0.0),
         where ``__call__`` returns its input.  There is no CPU fallback."""
-        from .pcm import _lengths
         if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
             raise RuntimeError("Resample.ragged (MI355X) needs a HIP tensor; no CPU fallback")
         if wav.dim() not in (2, 3) or min(wav.shape) < 1:
@@ -415,12 +355,10 @@ class Resample:
         y = torch.empty(B, self.out_len(N), device=wav.device, dtype=torch.float32)
         out_lens = torch.empty(B, device=wav.device, dtype=torch.int32)
         with torch.cuda.device(wav.device):
-            _check_mel(self.lib, self.lib.hfg_resample_ragged(
-                self.ptr, ctypes.c_void_p(wav.data_ptr()),
+            check(self.lib, self.lib.hfg_resample_ragged(
+                self.ptr, _ptr(wav),
                 _lib.PCM_DTYPES["int16" if wav.dtype == torch.int16 else "float32"], B, C, N,
-                ctypes.c_void_p(lens_t.data_ptr()) if lens_t is not None else None,
-                ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out_lens.data_ptr()),
-                ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+                _ptr(lens_t), _ptr(y), _ptr(out_lens), _stream(wav.device)))
         return y, out_lens
 
 
@@ -488,24 +426,7 @@ def read_wav(path: Union[str, Path]) -> Tuple[torch.Tensor, int]:
     """(waveform [channels, time] float32, sample_rate) from a RIFF/WAVE file, normalised
     as torchaudio.load does: integer PCM divided by 2^(bits-1) (8-bit: (v - 128) / 128),
     IEEE float as stored.  Host-side file parsing (torchaudio is absent in this image)."""
-    data = Path(path).read_bytes()
-    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise RuntimeError(f"{path}: not a RIFF/WAVE file")
-    pos, fmt, pcm = 12, None, None
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if cid == b"fmt ":
-            tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
-            if tag == 0xFFFE and len(body) >= 26:  # WAVE_FORMAT_EXTENSIBLE: subformat tag
-                tag = struct.unpack("<H", body[24:26])[0]
-            fmt = (tag, ch, sr, bits)
-        elif cid == b"data":
-            pcm = body
-        pos += 8 + size + (size & 1)
-    if fmt is None or pcm is None:
-        raise RuntimeError(f"{path}: missing fmt or data chunk")
-    tag, ch, sr, bits = fmt
+    (tag, ch, sr, bits), pcm = riff_chunks(path)
     width = bits // 8
     n = len(pcm) // (width * ch)
     pcm = pcm[:n * width * ch]
@@ -535,9 +456,7 @@ def extract_mel_from_file(audio_path: Union[str, Path], config: Optional[dict] =
     """data/audio_processing.py:142-164: (log-mel [n_mels, T], sample_rate).  The file is
     parsed on the host (read_wav) and the waveform moved to the HIP device."""
     waveform, sample_rate = read_wav(audio_path)
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    log_mel = extract_mel(waveform.to(device), sample_rate, config, config_path)
+    log_mel = extract_mel(waveform.to(default_device(device)), sample_rate, config, config_path)
     return log_mel, sample_rate
 
 

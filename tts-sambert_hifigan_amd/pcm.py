@@ -21,7 +21,6 @@ from __future__ import annotations
 
 import math
 import struct
-from ctypes import c_void_p
 from pathlib import Path
 from typing import Tuple, Union
 
@@ -29,20 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hifigan import _lengths_on
-
-
-def _check(lib, rc):
-    if rc != 0:
-        raise _lib.HfgError(rc, lib.hfg_mel_last_error().decode())
-
-
-def _stream(device) -> c_void_p:
-    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t) -> c_void_p:
-    return c_void_p(t.data_ptr()) if t is not None else None
+from ._frontend import (check as _check, lengths as _lengths, ptr as _ptr, riff_chunks,
+                        stream as _stream)
 
 
 def _dtype_code(wav) -> int:
@@ -59,23 +46,6 @@ def _rows(wav: torch.Tensor, who: str, dtypes) -> torch.Tensor:
         raise RuntimeError(f"pcm.{who}: expected {' or '.join(str(d) for d in dtypes)}, got "
                            f"{wav.dtype}")
     return wav.detach().contiguous()
-
-
-def _lengths(lengths, B: int, N: int, device):
-    """None, or the lengths as a device int32 [B]; host values are validated."""
-    if lengths is None:
-        return None
-    if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
-        host = torch.as_tensor(lengths)
-        if host.shape != (B,):
-            raise RuntimeError(f"lengths must have shape [{B}]")
-        if host.is_floating_point() or any(int(n) < 0 or int(n) > N for n in host.tolist()):
-            raise RuntimeError(f"every length must be an integer in [0, {N}], got "
-                               f"{host.tolist()}")
-    lens_t = _lengths_on(lengths, device)
-    if lens_t.shape != (B,):
-        raise RuntimeError(f"lengths must have shape [{B}]")
-    return lens_t
 
 
 def _peak(lib, wav, lens_t) -> torch.Tensor:
@@ -158,24 +128,7 @@ def to_pcm16(wav: torch.Tensor, lengths=None, rounding: str = "trunc", packed: b
 def read_wav_pcm16(path: Union[str, Path]) -> Tuple[torch.Tensor, int]:
     """(int16 [channels, time], sample_rate) from a 16-bit PCM RIFF/WAVE file, the samples as
     stored (``mel.read_wav`` returns them divided by 32768).  Any other encoding raises."""
-    data = Path(path).read_bytes()
-    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise RuntimeError(f"{path}: not a RIFF/WAVE file")
-    pos, fmt, pcm = 12, None, None
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if cid == b"fmt ":
-            tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
-            if tag == 0xFFFE and len(body) >= 26:  # WAVE_FORMAT_EXTENSIBLE: subformat tag
-                tag = struct.unpack("<H", body[24:26])[0]
-            fmt = (tag, ch, sr, bits)
-        elif cid == b"data":
-            pcm = body
-        pos += 8 + size + (size & 1)
-    if fmt is None or pcm is None:
-        raise RuntimeError(f"{path}: missing fmt or data chunk")
-    tag, ch, sr, bits = fmt
+    (tag, ch, sr, bits), pcm = riff_chunks(path)
     if tag != 1 or bits != 16 or ch < 1:
         raise RuntimeError(f"{path}: unsupported WAV encoding (format {tag}, {bits} bits); "
                            "read_wav_pcm16 takes 16-bit PCM only")
