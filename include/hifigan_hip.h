@@ -329,4 +329,11 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
  * ------------------------------------------------------------------------- */
 #include "hifigan_hip_resample.h"
 
+/* ---------------------------------------------------------------------------
+ * Forward-only spectral distances on the device (the mel of a wav against a held mel
+ * tensor, the multi-resolution log-STFT distance of two wavs), ragged batches,
+ * deterministic sums: the specdist section, in a header of its own.
+ * ------------------------------------------------------------------------- */
+#include "hifigan_hip_specdist.h"
+
 #endif /* HIFIGAN_HIP_H */

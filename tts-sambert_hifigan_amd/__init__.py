@@ -11,7 +11,8 @@ from ._lib import (HipExtensionMissing, HfgError, Handle, load_library, make_con
                    LIB_PATH, check_provenance, schedule_override, schedule_clear,
                    schedule_overrides)
 from . import pcm  # noqa: F401  (the release's PCM boundary: pcm.peak / to_float / to_pcm16)
+from . import metrics  # noqa: F401  (spectral distances: metrics.mel_distance / MultiResolutionSTFT)
 
 __all__ = ["HiFiGAN", "HiFiGANGenerator", "MRF", "ResBlock", "ResBlock2", "get_padding", "Handle",
            "HipExtensionMissing", "HfgError", "load_library", "make_config", "LIB_PATH", "check_provenance",
-           "schedule_override", "schedule_clear", "schedule_overrides", "pcm"]
+           "schedule_override", "schedule_clear", "schedule_overrides", "pcm", "metrics"]

@@ -266,6 +266,31 @@ RESAMPLE_EX_SIGNATURES = {
 RESAMPLE_MAX_CHANNELS = 8   # HFG_RESAMPLE_MAX_CHANNELS
 
 
+class HfgStftdistConfig(ctypes.Structure):
+    """hfg_stftdist_config: one STFT resolution; eps 0 selects the reference's 1e-5."""
+    _fields_ = [("n_fft", c_int32), ("hop_length", c_int32), ("win_length", c_int32),
+                ("eps", c_float)]
+
+
+# (handle, wav, B, n_samples, lengths, target, target_cols, ws, ws_bytes, sums, frames, stream)
+_MEL_DISTANCE = (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p])
+# every symbol declared in include/hifigan_hip_specdist.h (spectral distances)
+SPECDIST_SIGNATURES = {
+    "hfg_relmel_distance_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
+    "hfg_relmel_distance": _MEL_DISTANCE,
+    "hfg_mel_distance_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
+    "hfg_mel_distance": _MEL_DISTANCE,
+    "hfg_stftdist_create": (c_int, [POINTER(HfgStftdistConfig), c_int, POINTER(c_void_p)]),
+    "hfg_stftdist_destroy": (None, [c_void_p]),
+    "hfg_stftdist_set_window": (c_int, [c_void_p, POINTER(c_float)]),
+    "hfg_stftdist_frames": (c_int64, [c_void_p, c_int64]),
+    "hfg_stftdist_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
+    "hfg_stftdist_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                     c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+}
+
+
 def load_library(path: str = LIB_PATH):
     """Open libhifigan_hip.so (cached).  Raises HipExtensionMissing if absent."""
     global _lib
@@ -281,7 +306,7 @@ def load_library(path: str = LIB_PATH):
     allow_old = os.environ.get("HFG_ALLOW_OLD_LIB") == "1"
     missing = []
     for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES, **PCM_SIGNATURES,
-                              **RESAMPLE_EX_SIGNATURES}.items():
+                              **RESAMPLE_EX_SIGNATURES, **SPECDIST_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             missing.append(name)

@@ -4,6 +4,7 @@
 //   relmel_capi.cpp    hfg_relmel_*    the HiFi-GAN release's mel
 //   resample_capi.cpp  hfg_resample_*  torchaudio Resample, fixed-length and ragged
 //   pcm_capi.cpp       hfg_pcm_*       the release's PCM boundary
+//   specdist_capi.cpp  hfg_*_distance, hfg_stftdist_*   spectral distances
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,3 +63,26 @@ struct FftMelTables {
 };
 
 }  // namespace hfg_host
+
+// The two mel handles (created in mel_capi.cpp / relmel_capi.cpp; specdist_capi.cpp runs the
+// distance kernels on their tables).
+struct hfg_mel_handle {
+  hfg_mel_config cfg;
+  int device;
+  int n_bins, bins_pad;
+  // DFT-GEMM path: window-folded twiddles [n_fft][bins_pad] and the filterbank [n_bins][n_mels]
+  float* tcos = nullptr;
+  float* tsin = nullptr;
+  float* fb = nullptr;
+  std::vector<float> fb_host;
+  bool fft = false;  // logmel_fft (n_fft a power of two) on t's tables
+  int fpw = 2;
+  hfg_host::FftMelTables t;
+};
+
+struct hfg_relmel_handle {
+  hfg_relmel_config cfg;  // with fmax, spec_eps and clip_val resolved
+  int device;
+  int fpw;
+  hfg_host::FftMelTables t;
+};

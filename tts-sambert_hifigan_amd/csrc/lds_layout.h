@@ -222,6 +222,18 @@ constexpr size_t mel_fft_lds_total(int n_fft, int hop, int fpw, int n_mels) {
                           (size_t)n_mels * fpb);
 }
 
+// ---- mel_distance_fft / stft_distance_fft (spectral_distance.hip) ----
+// mel_distance_fft: the logmel_fft / release_mel_fft carve-up above (mel_fft_lds_total); the
+// four waves' partial sums overlay the FFT buffers once the frames are done.
+// stft_distance_fft: [the same FFT buffers][the block's span of signal a][of signal b], each
+// span fp32 and rounded up to 16 B; the wave partials overlay the FFT buffers likewise.
+__host__ __device__ constexpr int stft_dist_sig_stride(int span) { return (span + 3) & ~3; }  // floats
+constexpr size_t stft_dist_lds_total(int n_fft, int hop, int fpw) {
+  return mel_fft_sig_off(n_fft / 2) +
+         sizeof(float) * 2 *
+             (size_t)stft_dist_sig_stride(mel_fft_span(mel_fft_fpb(fpw), hop, n_fft));
+}
+
 // ---- resample_sinc / resample_ragged (resample.hip): [C channels][the input span of a
 // block's 256 outputs], C = 1 for resample_sinc; floats.  The 256 outputs cover at most
 // 255 / n_phases + 1 steps of `stride` input samples beyond the first output's klen taps. ----

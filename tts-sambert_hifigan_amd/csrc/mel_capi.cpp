@@ -136,20 +136,6 @@ void FftMelTables::free() {
 
 using namespace hfg_host;
 
-struct hfg_mel_handle {
-  hfg_mel_config cfg;
-  int device;
-  int n_bins, bins_pad;
-  // DFT-GEMM path: window-folded twiddles [n_fft][bins_pad] and the filterbank [n_bins][n_mels]
-  float* tcos = nullptr;
-  float* tsin = nullptr;
-  float* fb = nullptr;
-  std::vector<float> fb_host;
-  bool fft = false;  // logmel_fft (n_fft a power of two) on t's tables
-  int fpw = 2;
-  FftMelTables t;
-};
-
 namespace {
 
 // Build and upload every device table from a window [n_fft] and a filterbank

@@ -42,6 +42,38 @@ hipError_t launch_release_mel_fft(const float* wav, int64_t B, int64_t n_samp,
                                   const float* bw, int n_mels, float spec_eps, float clip,
                                   float* mel, int32_t* frame_lens, hipStream_t stream);
 
+// Spectral distances (spectral_distance.hip): two launches on `stream`, the distance kernel over
+// (blocks of 4 fpw frames, B) and specdist_finish; nothing allocated, no atomics.  For item b,
+// sums[b] = {sum |d|, sum d^2} (float64) over its compared frames and frames[b] their count.
+// lens as above (null = n_samp, clamped into [0, n_samp], samples at or past it never read).
+// ws: specdist_workspace_bytes(B, frames of n_samp, fpw) bytes, uninitialised.
+int64_t specdist_blocks(int64_t frames, int fpw);
+size_t specdist_workspace_bytes(int64_t B, int64_t frames, int fpw);
+// d = (float32 mel the front end would store) - target[b][m][f], f < min(frames(len_b), T);
+// target [B][n_mels][T] float32; the release framing (launch_release_mel_fft's arguments) ...
+hipError_t launch_release_mel_distance(const float* wav, int64_t B, int64_t n_samp,
+                                       const int32_t* lens, int n_fft, int hop, int fpw,
+                                       const float* window, const void* tw, const int* band,
+                                       const float* bw, int n_mels, float spec_eps, float clip,
+                                       const float* target, int64_t T, double* ws, double* sums,
+                                       int32_t* frames, hipStream_t stream);
+// ... and the reference's (launch_logmel_fft's), item b framed as if alone: len_b / hop + 1
+// frames when len_b > n_fft / 2, else 0
+hipError_t launch_logmel_distance(const float* wav, int64_t B, int64_t n_samp,
+                                  const int32_t* lens, int n_fft, int hop, int fpw,
+                                  const float* window, const void* tw, const int* band,
+                                  const float* bw, int n_mels, float eps, int log_mode,
+                                  float ln_base, const float* target, int64_t T, double* ws,
+                                  double* sums, int32_t* frames, hipStream_t stream);
+// d = (float) ln(|X_a[k]| + eps) - (float) ln(|X_b[k]| + eps), k = 0..n_fft/2, X the rfft of the
+// center=True reflect-padded frame times window (fp32 product); n_fft a power of two in
+// [16, 2048]
+size_t stft_distance_lds_bytes(int n_fft, int hop, int fpw);
+hipError_t launch_stft_distance(const float* a, const float* b, int64_t B, int64_t n_samp,
+                                const int32_t* lens, int n_fft, int hop, int fpw,
+                                const float* window, const void* tw, double eps, double* ws,
+                                double* sums, int32_t* frames, hipStream_t stream);
+
 // y[b][m] = sum_k x_pad[b][(m / n_phases) * stride + k] * kern[m % n_phases][k], m < n_out,
 // x_pad = x zero-padded by `width` on the left (torchaudio _apply_sinc_resample_kernel)
 hipError_t launch_resample(const float* x, int64_t B, int64_t n, int64_t n_out,

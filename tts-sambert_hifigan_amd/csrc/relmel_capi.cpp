@@ -7,13 +7,6 @@
 
 using namespace hfg_host;
 
-struct hfg_relmel_handle {
-  hfg_relmel_config cfg;  // with fmax, spec_eps and clip_val resolved
-  int device;
-  int fpw;
-  FftMelTables t;
-};
-
 namespace {
 
 // librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) (htk=False, norm="slaney") in double:

@@ -46,12 +46,20 @@ def _check_chain(gen, frontend) -> None:
     """The front end must frame at the Generator's hop and produce its n_mels."""
     import math
     hop = math.prod(int(u) for u in gen._hfg_args[1])
-    if frontend.hop_size != hop:
-        raise ValueError(f"front end hop_size {frontend.hop_size} != the Generator's "
+    fe_hop, fe_mels = _hop_and_mels(frontend)
+    if fe_hop != hop:
+        raise ValueError(f"front end hop_size {fe_hop} != the Generator's "
                          f"prod(upsample_rates) {hop}")
-    if frontend.num_mels != gen.n_mels:
-        raise ValueError(f"front end num_mels {frontend.num_mels} != the Generator's "
+    if fe_mels != gen.n_mels:
+        raise ValueError(f"front end num_mels {fe_mels} != the Generator's "
                          f"n_mels {gen.n_mels}")
+
+
+def _hop_and_mels(frontend):
+    """(hop, mel bands) of a mel.ReleaseMelSpectrogram or a mel.MelSpectrogram."""
+    if hasattr(frontend, "hop_size"):
+        return frontend.hop_size, frontend.num_mels
+    return frontend.hop, frontend.n_mels
 
 
 def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -65,6 +73,46 @@ def resynthesize(gen, frontend, wav: torch.Tensor, lengths=None) -> torch.Tensor
             return gen(frontend(wav))
         mel, frame_lengths = frontend(wav, lengths)
         return gen(mel, lengths=frame_lengths)
+
+
+def consistency(gen, frontend, mel: torch.Tensor, lengths=None):
+    """Does the audio realise its mel?  mel [B, n_mels, T] → ``(wav, SpectralDistance)``:
+    ``wav = gen(mel, lengths)`` and ``metrics.mel_distance(frontend, wav, mel, lengths * hop)``,
+    all on the device.  ``lengths`` (frames per item: ints or an int tensor, a device tensor is
+    never read back) makes item b compare its own ``lengths[b]`` frames.  With the release
+    front end ``frames(T * hop) == T``; the reference's ``mel.MelSpectrogram`` frames one more
+    and the first T are compared."""
+    from . import metrics
+    _check_chain(gen, frontend)
+    hop = _hop_and_mels(frontend)[0]
+    with torch.no_grad():
+        wav = gen(mel) if lengths is None else gen(mel, lengths=lengths)
+    if lengths is None:
+        sample_lengths = None
+    elif isinstance(lengths, torch.Tensor):
+        sample_lengths = lengths * hop
+    else:
+        sample_lengths = [int(n) * hop for n in lengths]
+    return wav, metrics.mel_distance(frontend, wav, mel, sample_lengths)
+
+
+def copy_synthesis_error(gen, frontend, wav: torch.Tensor, lengths=None):
+    """The release training loop's validation error on the device: wav [B, N] → ``frontend``
+    (``mel.ReleaseMelSpectrogram``) → ``gen`` → ``(wav_out, SpectralDistance)`` of
+    ``wav_out``'s mel against the very mel that was fed in (``.l1`` is the release's
+    ``F.l1_loss(y_mel, mel_spectrogram(y_g_hat))``).  ``wav_out`` is :func:`resynthesize`'s;
+    with ``lengths`` the front end's device frame counts drive the Generator and the distance:
+    no host round trip."""
+    from . import metrics
+    _check_chain(gen, frontend)
+    with torch.no_grad():
+        if lengths is None:
+            mel = frontend(wav)
+            out = gen(mel)
+            return out, metrics.mel_distance(frontend, out, mel)
+        mel, frame_lengths = frontend(wav, lengths)
+        out = gen(mel, lengths=frame_lengths)
+    return out, metrics.mel_distance(frontend, out, mel, frame_lengths * frontend.hop_size)
 
 
 _RESAMPLERS = {}
