@@ -24,11 +24,13 @@
 //   * A (weights): the host packs [m_tile][g][class][tap][plane][wave_m][wm][lane][8] bf16;
 //     the group's slab (128 * MT_c bf16) is copied to a 2-slot LDS ring by LDS-DMA one group
 //     ahead (no VGPRs).
-//   * B (lrelu'd, split input): the window of frames [m0-4, m0+NTILE+4) (quad-aligned, so
-//     every load is one 16-B dwordx4: 4 frames of one channel) is loaded one group ahead into
-//     registers, converted after the group's MFMAs and written as [frame][16 ch] bf16 hi / lo
-//     planes (16-B slots XOR-swizzled per 256-B block, xrow_off: conflict-free ds_read_b128
-//     for the three tap offsets -1, 0, +1, and staging writes within their transfer cycles).
+//   * B (lrelu'd, split input): the tile's frames [m0, m0+NTILE) (quad-aligned, so every load
+//     is one 16-B dwordx4: 4 frames of one channel; one quad x 4 channels per lane, every lane
+//     of every wave) and the two halo frames m0-1, m0+NTILE (dword loads, 16 lanes of wave 0)
+//     are loaded one group ahead into registers, converted after the group's MFMAs and written
+//     as [frame][16 ch] bf16 hi / lo planes of the window [m0-4, m0+NTILE+4) (16-B slots
+//     XOR-swizzled per 256-B block, xrow_off: conflict-free ds_read_b128 for the three tap
+//     offsets -1, 0, +1, and conflict-free ds_write_b64 staging writes).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -61,11 +63,11 @@ ups_bf16x3(const UpsParams p) {
   constexpr int NTILE = 32 * WN * WAVES_N;   // frames per block
   constexpr UpsLds LY = ups_lds(UpsCfg{WAVES_M, WAVES_N, WM, WN});  // lds_layout.h
   static_assert(LY.total <= (int)kMaxLdsBytes, "LDS");
-  constexpr int XR = LY.xr;                  // staged frames: [m0 - 4, m0 + NTILE + 4)
-  constexpr int NQ = XR / 4;                 // frame quads
-  constexpr int NTASK = 2 * NQ;              // (quad, 8-channel half) staging tasks
-  constexpr int TPW = (NTASK + NW - 1) / NW; // tasks per wave (one per lane)
-  static_assert(TPW <= 64, "one staging task per lane");
+  static_assert(LY.xr == NTILE + 8, "staged frames: [m0 - 4, m0 + NTILE + 4)");
+  // staging: the tile's NTILE / 4 frame quads x four 4-channel quarters are one sub-task per
+  // lane of every wave (16 quads per wave); the two halo frames m0 - 1 and m0 + NTILE (the
+  // only rows of the halo quads a tap reads) are 16 channel pairs on 16 lanes of wave 0
+  static_assert(NTILE == 64 * NW, "one (quad, 4-channel quarter) staging sub-task per lane");
   constexpr int XPLANE = LY.xplane;          // bytes per bf16 plane [frame][16 ch]
   constexpr int XBUF = LY.xbuf;              // hi + lo
   constexpr int SLAB = LY.slab;              // bytes: class x tap x plane x rows
@@ -74,10 +76,10 @@ ups_bf16x3(const UpsParams p) {
 
   // byte offset of (frame row r, 8-channel half h) in a staged plane: the 16-B slot 2r + h
   // XOR-swizzled inside its 256-B block by bits 2-3 of r.  The B reads (16 consecutive rows of
-  // one half per 16-lane group) stay conflict-free, and so do the staging writes (8 lanes =
-  // 4 quads x 2 halves, task order below), which the unswizzled layout put on 2 of the 8 16-B
-  // slots of a bank window (1.2 conflict cycles per LDS-active cycle; bank model
-  // tests/tools/ups_lds_banks.py)
+  // one half per 16-lane group) stay conflict-free, and so do the staging writes (16 lanes =
+  // 4 quads x 4 quarters of 8 B, sub-task order below), which the unswizzled layout put on 2
+  // of the 8 16-B slots of a bank window (1.2 conflict cycles per LDS-active
+  // cycle; bank models tests/tools/ups_lds_banks.py, profiles/ups_staging_ab/lds_banks_b64.py)
   auto xrow_off = [](int r, int h) {
     return 16 * ((2 * r + h) ^ (((r >> 3) & 1) * 5 + ((r >> 2) & 1) * 2));
   };
@@ -130,48 +132,62 @@ ups_bf16x3(const UpsParams p) {
     }
   };
 
-  // ---- input staging: one (quad, half) task per lane of the first TPW lanes ----
+  // ---- input staging: one (quad, 4-channel quarter) sub-task per lane of every wave ----
   // one buffer descriptor per 16-channel group (SGPR base + record count: a whole 4-GiB
   // item would not fit the 32-bit count); a quad outside its row reads offset 0 (masked)
   const char* xb = reinterpret_cast<const char*>(p.x + (int64_t)b * p.x_bs);
   const int64_t grp_bytes = (int64_t)16 * p.L * 4;
   const int grp_rec = (int)(unsigned)(grp_bytes < 0xFFFFFFFFll ? grp_bytes : 0xFFFFFFFFll);
-  const int task = wave * TPW + lane;
-  const bool has_task = lane < TPW && task < NTASK;
-  // (quad, half) interleaved: the 8 lanes of a ds_write_b128 group write 4 quads x both
-  // halves, which xrow_off's swizzle puts on the 8 distinct 16-B slots of a bank window
-  const int hf = task & 1;                   // channel half of the task
-  const int xq = task >> 1;                  // quad of the task
-  const int t0 = m0 - 4 + 4 * xq;            // first frame of the quad
+  // lane = 4 * (quad of the wave's 16) + quarter: the 16 lanes of a ds_write_b64 group write
+  // 4 quads x 4 quarters, which xrow_off's swizzle puts on the 16 distinct 8-B slots of a bank
+  // window (profiles/ups_staging_ab/lds_banks_b64.py); a load instruction reads 256 contiguous bytes of
+  // each of 4 channel rows
+  const int cq = lane & 3;                   // channels 4 cq .. 4 cq + 3 of the group
+  const int hf = cq >> 1;                    // their 8-channel half (16-B slot of a frame row)
+  const int xq = 1 + wave * 16 + (lane >> 2);  // window quad (quad 0 holds the left halo)
+  const int t0 = m0 - 4 + 4 * xq;            // first frame of the quad, >= m0
   // leaky_relu as max(v * sx, v * 0.1 sx) (f16x3 scale sx; bitwise max(v, 0.1 v) for bf16x3)
   // and the zero padding as a select: frames in [T_b, L) of a ragged item were never written
   // (0 * NaN would be NaN), and the polyphase kernel reads no such frame
   const float sx1 = kLReluSlope * sx;
   bool okt[4];
 #pragma unroll
-  for (int tt = 0; tt < 4; ++tt) okt[tt] = has_task && (unsigned)(t0 + tt) < (unsigned)T_b;
+  for (int tt = 0; tt < 4; ++tt) okt[tt] = (unsigned)(t0 + tt) < (unsigned)T_b;
   // whole quads only (L % 4 == 0, host-checked): a quad is inside the row or wholly outside
-  const bool q_in = has_task && t0 >= 0 && t0 < p.L;
-  const unsigned xoff_lane = q_in ? (unsigned)(8 * hf * p.L + t0) * 4u : 0u;
+  const bool q_in = t0 < p.L;
+  const unsigned xoff_lane = q_in ? (unsigned)(4 * cq * p.L + t0) * 4u : 0u;
   const int xcs4 = p.L * 4;
+  // halo: lane l of wave 0 (wave-uniform branch) loads channel pair l & 7 of frame m0 - 1
+  // (window row 3; bit 3 of l clear) or m0 + NTILE (row NTILE + 4); lanes 0-15 write them
+  const int hcp = lane & 7;
+  const int hrow = lane & 8 ? NTILE + 4 : 3;
+  const int ht = m0 - 4 + hrow;
+  const bool hok = (unsigned)ht < (unsigned)T_b;  // T_b <= L: inside the row
+  const unsigned hoff_lane = hok ? (unsigned)(2 * hcp * p.L + ht) * 4u : 0u;
   typedef float f4 __attribute__((ext_vector_type(4)));
-  f4 xv[8];
+  f4 xv[4];
+  float hx[2];
   auto load_x = [&](int g) {
     const __amdgpu_buffer_rsrc_t xrs =
         __builtin_amdgcn_make_buffer_rsrc((void*)(xb + g * grp_bytes), 0, grp_rec, 0x00020000);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
+    for (int e = 0; e < 4; ++e)
       xv[e] = __builtin_bit_cast(
           f4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)xoff_lane, e * xcs4, 0));
+    if (wave == 0) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        hx[e] = __builtin_bit_cast(
+            float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)hoff_lane, e * xcs4, 0));
+    }
   };
   auto store_x = [&](int buf) {
-    if (!has_task) return;
     char* xh = Xbuf + buf * XBUF;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      bf16x8 hv, lv;
+      bf16x4_ hv, lv;
 #pragma unroll
-      for (int e = 0; e < 8; e += 2) {
+      for (int e = 0; e < 4; e += 2) {
         floatx2_ a;
         a[0] = okt[j] ? fmaxf(xv[e][j] * sx, xv[e][j] * sx1) : 0.f;
         a[1] = okt[j] ? fmaxf(xv[e + 1][j] * sx, xv[e + 1][j] * sx1) : 0.f;
@@ -182,9 +198,19 @@ ups_bf16x3(const UpsParams p) {
         lv[e] = ll[0];
         lv[e + 1] = ll[1];
       }
-      const int off = xrow_off(4 * xq + j, hf);
-      *reinterpret_cast<bf16x8*>(xh + off) = hv;
-      *reinterpret_cast<bf16x8*>(xh + XPLANE + off) = lv;
+      const int off = xrow_off(4 * xq + j, hf) + 8 * (cq & 1);
+      *reinterpret_cast<bf16x4_*>(xh + off) = hv;
+      *reinterpret_cast<bf16x4_*>(xh + XPLANE + off) = lv;
+    }
+    if (wave == 0 && lane < 16) {
+      floatx2_ a;
+      a[0] = hok ? fmaxf(hx[0] * sx, hx[0] * sx1) : 0.f;
+      a[1] = hok ? fmaxf(hx[1] * sx, hx[1] * sx1) : 0.f;
+      bf16x2_ hh, ll;
+      split2<FMT>(a, hh, ll);
+      const int off = xrow_off(hrow, hcp >> 2) + 4 * (hcp & 3);
+      *reinterpret_cast<bf16x2_*>(xh + off) = hh;
+      *reinterpret_cast<bf16x2_*>(xh + XPLANE + off) = ll;
     }
   };
 
@@ -267,6 +293,20 @@ ups_bf16x3(const UpsParams p) {
 #pragma unroll
   for (int i = 0; i < WM; ++i) {
     const int rb = mt * MT + wave_m * 32 * WM + i * 32 + 4 * half;  // row of r = 0
+    // the lane's bias values, loaded before the first store: a load behind stores in the one
+    // in-order vmcnt queue would wait for them (the layer epilogue keeps its bias in LDS for
+    // the same reason)
+    float bvr[16];
+    if (h == 1) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bvr[r] = p.bias[rb + acc_row(r)];
+    } else if (h == 2) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) bvr[q] = p.bias[(rb + 8 * (q >> 1) + 2 * (q & 1)) >> 1];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bvr[q] = p.bias[(rb + 8 * q) / h];
+    }
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
       const int m = m0 + wave_n * 32 * WN + k * 32 + col;
@@ -282,7 +322,7 @@ ups_bf16x3(const UpsParams p) {
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
           const int co0 = rb + acc_row(r);
-          const float b0 = p.bias[co0], b1 = p.bias[co0 + 1];
+          const float b0 = bvr[r], b1 = bvr[r + 1];
           const float l0 = __builtin_fmaf(acc[0][i][k][r], sc, b0);
           const float r0 = __builtin_fmaf(acc[1][i][k][r], sc, b0);
           const float l1 = __builtin_fmaf(acc[0][i][k][r + 1], sc, b1);
@@ -320,7 +360,7 @@ ups_bf16x3(const UpsParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int co = rb + acc_row(r);
-          const float bv = p.bias[co];
+          const float bv = bvr[r];
           floatx2_ v;
           v[0] = __builtin_fmaf(acc[0][i][k][r], sc, bv);
           v[1] = __builtin_fmaf(acc[1][i][k][r], sc, bv);
@@ -335,7 +375,7 @@ ups_bf16x3(const UpsParams p) {
           for (int pr = 0; pr < 2; ++pr) {
             const int r0 = 4 * q + 2 * pr;
             const int co = (rb + 8 * q + 2 * pr) >> 1;
-            const float bv = p.bias[co];
+            const float bv = bvr[2 * q + pr];
             float4 v;
             v.x = __builtin_fmaf(acc[0][i][k][r0], sc, bv);
             v.y = __builtin_fmaf(acc[0][i][k][r0 + 1], sc, bv);
@@ -351,7 +391,7 @@ ups_bf16x3(const UpsParams p) {
         for (int q = 0; q < 4; ++q) {
           const int row = rb + 8 * q;
           const int co = row / h, sp = row - co * h;
-          const float bv = p.bias[co];
+          const float bv = bvr[q];
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
             float4 v;
