@@ -72,6 +72,20 @@ int hfg_debug_thin_window(int C, int mfma);
  * for. */
 int64_t hfg_debug_lds_bytes(const char* family, const int* args, int n_args);
 
+/* The workspace layout of a forward as JSON in buf (NUL-terminated): what hfg_workspace_bytes
+ * (hfg_mrf_workspace_bytes) totals and the launch schedule takes every pointer from.
+ *   {"total": bytes, "parts": [{"b0", "B", "off", "bytes", "regions": [{"name", "off", "bytes"}]}]}
+ * A generator handle (B, T frames): one part, or the two batch halves [b0, b0 + B) of a split
+ * forward; per part the regions "X", "R", "Tb", "MRF", with concurrent ResBlocks "rb<j>.R",
+ * "rb<j>.Tb", "rb<j>.out" per ResBlock, "table" (per-stage lengths) and "slots" (f16x3
+ * scales, 0 bytes in the unscaled modes).  taps != 0: the layout hfg_forward_taps runs, the
+ * whole batch as one part; its total never exceeds hfg_workspace_bytes, which covers both.
+ * An MRF handle (B, L samples; taps ignored): one part of "R", "Tb" and "slots".  Offsets are
+ * bytes from the workspace's start, 256-byte aligned.  Host-only handles included; no commit.
+ * HFG_EINVAL when buflen is too small. */
+int hfg_debug_workspace(const hfg_handle* h, int64_t B, int64_t T_or_L, int taps, char* buf,
+                        size_t buflen);
+
 /* A Generator forward (one stream) that also copies the stage outputs the
  * reference's forward passes through (models/hifigan.py:238-251) into
  * caller-owned device buffers: taps[0] <- conv_pre [B][C0][T], taps[1 + 2i] <-

@@ -193,6 +193,7 @@ SIGNATURES = {
     "hfg_debug_plan": (c_int, [c_void_p, c_char_p, c_size_t]),
     "hfg_debug_thin_window": (c_int, [c_int, c_int]),
     "hfg_debug_lds_bytes": (c_int64, [c_char_p, POINTER(c_int), c_int]),
+    "hfg_debug_workspace": (c_int, [c_void_p, c_int64, c_int64, c_int, c_char_p, c_size_t]),
     "hfg_mrf_create": (c_int, [POINTER(HfgMrfConfig), c_int, POINTER(c_void_p)]),
     "hfg_mrf_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
     "hfg_mrf_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
@@ -494,6 +495,16 @@ class Handle:
         import json
         buf = ctypes.create_string_buffer(1 << 20)
         check(self.lib.hfg_debug_plan(self.ptr, buf, len(buf)))
+        return json.loads(buf.value.decode())
+
+    def workspace_layout(self, B: int, T: int, taps: bool = False) -> dict:
+        """The workspace layout of a forward of B items of T frames (an MRF handle: T
+        samples): total, parts and their regions (hfg_debug_workspace); ``taps``: the
+        one-part layout of ``forward_taps``."""
+        import json
+        buf = ctypes.create_string_buffer(1 << 14)
+        check(self.lib.hfg_debug_workspace(self.ptr, int(B), int(T), 1 if taps else 0, buf,
+                                           len(buf)))
         return json.loads(buf.value.decode())
 
     def packed_layer(self, mod: str):

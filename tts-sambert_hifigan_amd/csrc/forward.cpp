@@ -77,6 +77,19 @@ hipEvent_t pool_event(hfg_handle* h) {
   return e;
 }
 
+// An activation tensor and the f16x3 scale slot its producer commits (null in the unscaled
+// modes, and for a tensor no launch reads a scale of); Src: the same for a tensor only read
+// (a caller's input: its slot is written by an absmax pass).
+struct Src {
+  const float* p = nullptr;
+  uint32_t* amax = nullptr;
+};
+struct Act {
+  float* p = nullptr;
+  uint32_t* amax = nullptr;
+  operator Src() const { return {p, amax}; }
+};
+
 // f16x3 activation scales of one forward part (bf16x3_common.h): slot rows handed out in
 // launch order; base null in the unscaled modes (every take() is then null)
 struct Slots {
@@ -84,13 +97,12 @@ struct Slots {
   int n = 0, next = 0;
   int64_t B = 0;
   bool overflow = false;
-  // f16x3: the slots at `at` (slots_bytes(h, B) of the workspace), zeroed on the stream
-  int begin(const hfg_handle* h, void* at, int64_t batch, hipStream_t stream) {
-    if (h->fmt != hfg::kFmtF16) return HFG_OK;
-    base = static_cast<uint32_t*>(at);
+  // the part's slot region (absent unless f16x3), zeroed on the stream
+  int begin(const hfg_handle* h, uint32_t* at, const WsPart& part, hipStream_t stream) {
+    if (!(base = at)) return HFG_OK;
     n = n_slots(h);
-    B = batch;
-    hipError_t e = hipMemsetAsync(base, 0, slots_bytes(h, B), stream);
+    B = part.B;
+    hipError_t e = hipMemsetAsync(base, 0, part.slots.bytes, stream);
     return e == hipSuccess ? HFG_OK : hip_fail(e, "hipMemsetAsync(scale slots)");
   }
   uint32_t* take() {
@@ -108,13 +120,22 @@ struct Slots {
 
 struct Launcher {
   hfg_handle* h;
+  void* ws;  // the caller's workspace
   hipStream_t stream;
   int part = 0;
   int seq = 0;
   int conc = 1;  // launches of this schedule running side by side (concurrent ResBlocks)
   Slots* sl = nullptr;
   ProfRec* rec = nullptr;
-  uint32_t* take() { return sl ? sl->take() : nullptr; }
+  // The one "base + offset" into the workspace: every pointer of a forward is a region of
+  // its layout (handle.h, WsLayout); null for an absent region.
+  template <class T>
+  T* at(const WsRegion& r) const {
+    return r.bytes ? reinterpret_cast<T*>(static_cast<char*>(ws) + r.off) : nullptr;
+  }
+  // the tensor the next producing launch writes, with the next scale slot
+  Act act(float* p) { return {p, sl ? sl->take() : nullptr}; }
+  Src act(const float* p) { return {p, sl ? sl->take() : nullptr}; }
   void begin(double flop, double bytes) {
     rec = nullptr;
     if (!h->profiling) return;
@@ -130,28 +151,33 @@ struct Launcher {
   }
 };
 
-// What a Conv1d and a polyphase ConvTranspose1d launch share: x [B][C_in][Lin] ->
-// y [B][C_out][Lout] as a GEMM of L.M rows x L.KT taps.
-// ain / aout: f16x3 scale slots of the input (its producer's) and of this launch's output
-ConvParams layer_params(const hfg_handle* h, const Layer& L, const float* x, int64_t Lin, float* y,
-                        int64_t Lout, const int32_t* len_in, const int32_t* len_out,
-                        const uint32_t* ain, uint32_t* aout) {
+// What is constant for one stage of one part: the batch, the stage's length and the row of
+// the part's length table (null: every item L long).
+struct Dims {
+  int64_t B, L;
+  const int32_t* lens;
+};
+
+// What a Conv1d and a polyphase ConvTranspose1d launch share: x [B][C_in][in.L] ->
+// y [B][C_out][out.L] as a GEMM of L.M rows x L.KT taps, each side with its scale slot.
+ConvParams layer_params(const hfg_handle* h, const Layer& L, const Dims& in, Src x,
+                        const Dims& out, Act y) {
   ConvParams p{};
-  p.x = x;
-  p.x_bs = (int64_t)L.C_in * Lin;
-  p.x_cs = Lin;
+  p.x = x.p;
+  p.x_bs = (int64_t)L.C_in * in.L;
+  p.x_cs = in.L;
   p.x_ts = 1;
   p.C_in = L.C_in;
-  p.L_in = (int)Lin;
-  p.len_in = len_in;
-  p.len_out = len_out;
-  p.y = y;
-  p.y_bs = (int64_t)L.C_out * Lout;
+  p.L_in = (int)in.L;
+  p.len_in = in.lens;
+  p.len_out = out.lens;
+  p.y = y.p;
+  p.y_bs = (int64_t)L.C_out * out.L;
   p.M = L.M;
   p.dil = L.dil;
   p.kt = L.KT;
-  p.amax_in = ain;
-  p.amax_out = aout;
+  p.amax_in = x.amax;
+  p.amax_out = y.amax;
   p.ew = L.ew;
   p.dbg = h->dbg_flags;
   return p;
@@ -161,8 +187,9 @@ ConvParams layer_params(const hfg_handle* h, const Layer& L, const float* x, int
 // layer whose own tile would leave most CUs idle, fewer than kSmallGridBlocks blocks over
 // the `conc` launches that share the chip, runs the small tile on its own packing: bitwise
 // the same result, kernels.h tile 4), the profile record, the kernel of the layer's precision.
-int launch_layer(hfg_handle* h, Launcher& ln, const Layer& L, ConvParams& p, bool ups, int64_t B,
-                 double flop, double bytes) {
+int launch_layer(Launcher& ln, const Layer& L, ConvParams& p, bool ups, int64_t B, double flop,
+                 double bytes) {
+  hfg_handle* h = ln.h;
   auto n_tiles_of = [&](const Packing& pk) {
     const int nt = L.prec == 1 ? hfg::kBf16x3Tiles[pk.tile].NTILE() : kTiles[pk.tile].NTILE();
     return (p.N + nt - 1) / nt;
@@ -188,30 +215,60 @@ int launch_layer(hfg_handle* h, Launcher& ln, const Layer& L, ConvParams& p, boo
   return HFG_OK;
 }
 
-// One conv-layer launch (regular Conv1d).
-int run_conv(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t B, int64_t Lt,
-             float* y, bool act_in, bool act_out, const float* res, float* mrf, int mrf_mode,
-             float mrf_div, const int32_t* lens, const uint32_t* ain, uint32_t* aout,
-             bool x_btc = false) {
-  ConvParams p = layer_params(h, L, x, Lt, y, Lt, lens, lens, ain, aout);
-  if (x_btc) {  // [B][T][C] (acoustic-model layout) instead of [B][C][T]
+struct PostFuse {
+  const float* w;  // conv_post weight [C][7], bias [1] (packed fp32)
+  const float* b;
+  float* wav;      // [B][L]
+  float slope;     // of the leaky_relu in front of conv_post (post_slope_of)
+};
+
+// Where a ResBlock's result goes in the MRF: y combined by the epilogue mode (bit0 add, bit1
+// divide by div), amax the slot of y where this write completes it, post the conv_post +
+// tanh fused into a whole-ResBlock launch that is the network's last MRF write.
+struct MrfOut {
+  float* y = nullptr;
+  int mode = 0;
+  float div = 1.f;
+  uint32_t* amax = nullptr;
+  const PostFuse* post = nullptr;
+};
+
+// What a conv launch does around its GEMM, named where it is asked for.
+struct ConvOpts {
+  bool act_in = false, act_out = false, x_btc = false;
+  const float* res = nullptr;
+  ConvOpts& lrelu_in() { return act_in = true, *this; }
+  ConvOpts& lrelu_out() { return act_out = true, *this; }
+  ConvOpts& residual(const float* r) { return res = r, *this; }
+  // x is [B][T][C] (acoustic-model layout) instead of [B][C][T]
+  ConvOpts& btc_input(bool on) { return x_btc = on, *this; }
+};
+
+// One conv-layer launch (regular Conv1d): y = conv(x), or with mrf the ResBlock's last conv,
+// whose result goes to the MRF epilogue instead of y.
+int run_conv(Launcher& ln, const Layer& L, const Dims& d, Src x, Act y, const ConvOpts& o,
+             const MrfOut* mrf = nullptr) {
+  if (mrf) y = Act{nullptr, mrf->amax};
+  ConvParams p = layer_params(ln.h, L, d, x, d, y);
+  if (o.x_btc) {
     p.x_cs = 1;
     p.x_ts = L.C_in;
   }
+  const int64_t B = d.B, Lt = d.L;
   p.N = (int)Lt;
   p.off = -L.pad;
-  p.act_in = act_in;
-  p.act_out = act_out;
-  p.res = res;
-  p.mrf = mrf;
-  p.mrf_mode = mrf_mode;
-  p.mrf_div = mrf_div;
+  p.act_in = o.act_in;
+  p.act_out = o.act_out;
+  p.res = o.res;
+  p.mrf = mrf ? mrf->y : nullptr;
+  p.mrf_mode = mrf ? mrf->mode : 0;
+  p.mrf_div = mrf ? mrf->div : 1.f;
   p.epi_lds = 1;
   const double flop = 2.0 * L.C_out * L.C_in * L.k * (double)Lt * B;
   double bytes = 4.0 * B * Lt * (L.C_in + L.C_out) + 4.0 * L.C_out * L.C_in * L.k;
-  if (res) bytes += 4.0 * B * Lt * L.C_out;
-  if (mrf && (mrf_mode & 1)) bytes += 4.0 * B * Lt * L.C_out;
-  return launch_layer(h, ln, L, p, false, B, flop, bytes);
+  if (o.res) bytes += 4.0 * B * Lt * L.C_out;
+  if (mrf && (mrf->mode & 1)) bytes += 4.0 * B * Lt * L.C_out;
+  return launch_layer(ln, L, p, false, B, flop, bytes);
 }
 
 // slope of the leaky_relu in front of conv_post: the reference's 0.1 (models/hifigan.py:254)
@@ -220,21 +277,16 @@ inline float post_slope_of(const hfg_handle* h) {
   return h->cfg.post_slope ? h->cfg.post_slope : hfg::kLReluSlope;
 }
 
-struct PostFuse {
-  const float* w;  // conv_post weight [C][7], bias [1] (packed fp32)
-  const float* b;
-  float* wav;      // [B][L]
-  float slope;     // of the leaky_relu in front of conv_post (post_slope_of)
-};
-
 // One whole ResBlock (all dilations) + its MRF contribution in one launch.
 // A split ResBlock (rb.split) runs as two launches through `scratch` (B*C*L floats): convs
 // [0, split) write x after their dilation pairs (MRF-epilogue mode 0: a plain store), convs
 // [split, n) read it back and do the MRF epilogue.  fp32 round trip: bitwise the same x.
-// post: conv_post + tanh fused into the last launch (C = 32, the network's last MRF write).
-int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x, int64_t B,
-                 int64_t Lt, float* mrf, int mrf_mode, float mrf_div, const int32_t* lens,
-                 float* scratch, uint32_t* aout, const PostFuse* post = nullptr) {
+// out.post: conv_post + tanh fused into the last launch (C = 32, the network's last MRF write).
+int run_resblock(Launcher& ln, const RbFused& rb, const Dims& d, const float* x, float* scratch,
+                 const MrfOut& out) {
+  hfg_handle* h = ln.h;
+  const int64_t B = d.B, Lt = d.L;
+  const PostFuse* post = out.post;
   const Layer& L0 = h->layers[rb.convs[0]];
   const int C = L0.C_out;
   const int n_all = (int)rb.convs.size();
@@ -247,7 +299,7 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     p.x = part == 0 ? x : scratch;
     p.bs = (int64_t)C * Lt;
     p.L = (int)Lt;
-    p.len = lens;
+    p.len = d.lens;
     p.w = reinterpret_cast<const __bf16*>(h->packed_dev + rb.w_off);
     p.w_bytes = (int)(rb.w_len * sizeof(float));
     p.bias = h->packed_dev + rb.b_off + (size_t)c0 * C;
@@ -263,11 +315,11 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     }
     p.halo = n_part == 1 ? rb.halo : rb.halo_p[part];
     p.W = n_part == 1 ? rb.W : rb.W_p[part];
-    p.mrf = last ? mrf : scratch;
-    p.mrf_mode = last ? mrf_mode : 0;
-    p.mrf_div = mrf_div;
-    p.mrf_rcp = hfg::fast_div_ok(mrf_div) ? 1.0f / mrf_div : 0.0f;
-    p.amax_out = last ? aout : nullptr;
+    p.mrf = last ? out.y : scratch;
+    p.mrf_mode = last ? out.mode : 0;
+    p.mrf_div = out.div;
+    p.mrf_rcp = hfg::fast_div_ok(out.div) ? 1.0f / out.div : 0.0f;
+    p.amax_out = last ? out.amax : nullptr;
     p.dbg = h->dbg_flags;
     // resident blocks per CU from the LDS footprint
     const int per_cu = hfg::rb_lds_bytes(C, rb.nwin, n_all) <= hfg::kMaxLdsBytes / 2 ? 2 : 1;
@@ -279,7 +331,7 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
     if (h->rb_persist && per_cu == 1 && !(last && post) && !rb2)
       p.persist = std::max(1, h->n_cu / (h->rb_persist == 1 ? h->halves : 1));
     double bytes =
-        4.0 * B * Lt * C * ((last && (mrf_mode & 1)) ? 3 : 2) + 4.0 * (double)rb.w_len;
+        4.0 * B * Lt * C * ((last && (out.mode & 1)) ? 3 : 2) + 4.0 * (double)rb.w_len;
     if (last && post) {
       // the stage output is exact on the centre plus conv_post's radius on either side
       p.halo = rb.halo_post;
@@ -305,9 +357,10 @@ int run_resblock(hfg_handle* h, Launcher& ln, const RbFused& rb, const float* x,
   return HFG_OK;
 }
 
-int run_ups(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t B, int64_t Lin,
-            int64_t Lout, float* y, const int32_t* len_in, const int32_t* len_out,
-            const uint32_t* ain, uint32_t* aout) {
+// lrelu -> ConvTranspose1d: x [B][C_in][in.L] -> y [B][C_out][out.L]
+int run_ups(Launcher& ln, const Layer& L, const Dims& in, Src x, const Dims& out, Act y) {
+  hfg_handle* h = ln.h;
+  const int64_t B = in.B, Lin = in.L, Lout = out.L;
   const double flop = 2.0 * L.C_in * L.C_out * L.k * (double)Lin * B;
   const double bytes = 4.0 * B * (L.C_in * Lin + L.C_out * Lout) + 4.0 * L.C_in * L.C_out * L.k;
   if (L.ups_cfg >= 0 && h->ups_frames && Lin % 4 == 0 && Lout == Lin * L.s) {
@@ -319,15 +372,15 @@ int run_ups(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t
     if (h->ups_frames == 2 ||
         (int64_t)L.m_tiles_f * n_tiles * B * ln.conc >= hfg::kSmallGridBlocks) {
       hfg::UpsParams q{};
-      q.x = x;
+      q.x = x.p;
       q.x_bs = (int64_t)L.C_in * Lin;
       q.C_in = L.C_in;
       q.L = (int)Lin;
       q.T = (int)Lin;
-      q.len_in = len_in;
+      q.len_in = in.lens;
       q.w = reinterpret_cast<const __bf16*>(h->packed_dev + L.wf_off);
       q.bias = h->packed_dev + L.bf_off;
-      q.y = y;
+      q.y = y.p;
       q.y_bs = (int64_t)L.C_out * Lout;
       q.C_out = L.C_out;
       q.L_out = (int)Lout;
@@ -335,8 +388,8 @@ int run_ups(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t
       q.m_tiles = L.m_tiles_f;
       q.n_tiles = n_tiles;
       q.batch = (int)B;
-      q.amax_in = ain;
-      q.amax_out = aout;
+      q.amax_in = x.amax;
+      q.amax_out = y.amax;
       q.ew = L.ew;
       q.dbg = h->dbg_flags;
       const char* name = nullptr;
@@ -348,7 +401,7 @@ int run_ups(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t
       return HFG_OK;
     }
   }
-  ConvParams p = layer_params(h, L, x, Lin, y, Lout, len_in, len_out, ain, aout);
+  ConvParams p = layer_params(h, L, in, x, out, y);
   // columns u: t_out + p = s*u + r  for t_out in [0, Lout)
   p.N = (int)((Lout - 1 + L.p) / L.s + 1);
   p.off = -(L.KT - 1);
@@ -357,19 +410,20 @@ int run_ups(hfg_handle* h, Launcher& ln, const Layer& L, const float* x, int64_t
   p.ups_p = L.p;
   p.ups_swz = 1;
   p.L_out = (int)Lout;
-  return launch_layer(h, ln, L, p, true, B, flop, bytes);
+  return launch_layer(ln, L, p, true, B, flop, bytes);
 }
 
 // A thin stage's whole MRF (or ResBlock only_j alone) in one mrf_thin launch.
-int run_thin(hfg_handle* h, Launcher& ln, const Stage& st, const float* X, int64_t B, int64_t Lt,
-             float* out, const int32_t* lens, int only_j, uint32_t* aout) {
+int run_thin(Launcher& ln, const Stage& st, const Dims& d, const float* X, Act out, int only_j) {
+  hfg_handle* h = ln.h;
+  const int64_t B = d.B, Lt = d.L;
   const hfg_config& c = h->cfg;
   const int C = st.C;
   hfg::ThinParams p{};
   p.x = X;
   p.bs = (int64_t)C * Lt;
   p.L = (int)Lt;
-  p.len = lens;
+  p.len = d.lens;
   p.w = h->packed_dev;
   const int j0 = only_j >= 0 ? only_j : 0, j1 = only_j >= 0 ? only_j + 1 : c.n_res;
   p.n_res = j1 - j0;
@@ -395,9 +449,9 @@ int run_thin(hfg_handle* h, Launcher& ln, const Stage& st, const float* X, int64
   p.bias = h->packed_dev + st.thin_b_off + (size_t)cv_base * C;
   p.halo = halo;
   p.W = (st.thin_mfma ? hfg::thin_mfma_window(C) : hfg::thin_window(C)) - 2 * halo;
-  p.y = out;
+  p.y = out.p;
   p.div = (float)p.n_res;
-  p.amax_out = aout;
+  p.amax_out = out.amax;
   if (st.thin_mfma) {
     const int base = st.thin_m_conv[cv_base];
     p.wm = reinterpret_cast<const __bf16*>(h->packed_dev + st.thin_m_off) + base / 2;
@@ -416,67 +470,44 @@ int run_thin(hfg_handle* h, Launcher& ln, const Stage& st, const float* X, int64
 }
 
 // ResBlock j of stage st (ResBlock.forward, models/hifigan.py:72-86) on X, its result
-// combined into out by the MRF epilogue mode (bit0 add, bit1 divide by n_res); idx = index
-// of its first dilation in st.conv1 / st.conv2.  R, Tb: scratch of the layer-per-launch path.
-// f16x3: ax = scale slot of X; aout = slot of out (committed by the write that completes it)
-int run_one_rb(hfg_handle* h, Launcher& ln, const Stage& st, int j, int idx, const float* X,
-               int64_t B, int64_t L, float* R, float* Tb, float* out, int mode,
-               const int32_t* lens, const uint32_t* ax, uint32_t* aout,
-               const PostFuse* post = nullptr) {
+// combined into the MRF as `out` says; b: scratch of the layer-per-launch path (b.Tb: also of
+// a split whole-ResBlock launch).
+int run_one_rb(Launcher& ln, const Stage& st, int j, const Dims& d, Src X, const WsRbRegions& b,
+               const MrfOut& out) {
+  hfg_handle* h = ln.h;
   const hfg_config& c = h->cfg;
-  if (st.rbs[j].fused)
-    return run_resblock(h, ln, st.rbs[j], X, B, L, out, mode, (float)c.n_res, lens, Tb, aout,
-                        post);
+  float *R = ln.at<float>(b.R), *Tb = ln.at<float>(b.Tb);
+  if (st.rbs[j].fused) return run_resblock(ln, st.rbs[j], d, X.p, Tb, out);
+  // index of the block's first dilation in st.conv1 / st.conv2
+  int idx = 0;
+  for (int q = 0; q < j; ++q) idx += c.n_dil[q];
   int rc;
-  const uint32_t* asrc = ax;
-  if (c.resblock_type == 1) {
-    // ResBlock2, one launch per dilation: x = x + conv_m(lrelu(x)).  The conv reads a
-    // neighbourhood of x, so it writes the other of R / Tb; the last one carries the MRF epilogue
-    const float* src = X;
-    for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
-      const Layer& Lm = h->layers[st.conv1[idx]];
-      if (m < c.n_dil[j] - 1) {
-        float* dst = (m & 1) ? Tb : R;
-        uint32_t* ar = ln.take();
-        rc = run_conv(h, ln, Lm, src, B, L, dst, true, false, src, nullptr, 0, 1.f, lens, asrc, ar);
-        src = dst;
-        asrc = ar;
-      } else {
-        rc = run_conv(h, ln, Lm, src, B, L, nullptr, true, false, src, out, mode, (float)c.n_res,
-                      lens, asrc, aout);
-      }
-      if (rc) return rc;
-    }
-    return HFG_OK;
-  }
+  Src src = X;
   for (int m = 0; m < c.n_dil[j]; ++m, ++idx) {
-    const float* src = (m == 0) ? X : R;
+    const bool last = m == c.n_dil[j] - 1;
     const Layer& L1 = h->layers[st.conv1[idx]];
-    const Layer& L2 = h->layers[st.conv2[idx]];
-    // xt = lrelu(conv1(lrelu(x)))
-    uint32_t* at = ln.take();
-    rc = run_conv(h, ln, L1, src, B, L, Tb, true, true, nullptr, nullptr, 0, 1.f, lens, asrc, at);
-    if (rc) return rc;
-    if (m < c.n_dil[j] - 1) {
-      // x = x + conv2(xt)
-      uint32_t* ar = ln.take();
-      rc = run_conv(h, ln, L2, Tb, B, L, R, false, false, src, nullptr, 0, 1.f, lens, at, ar);
-      asrc = ar;
-    } else {
-      rc = run_conv(h, ln, L2, Tb, B, L, nullptr, false, false, src, out, mode, (float)c.n_res,
-                    lens, at, aout);
+    if (c.resblock_type == 1) {
+      // ResBlock2, one launch per dilation: x = x + conv_m(lrelu(x)).  The conv reads a
+      // neighbourhood of x, so it writes the other of R / Tb; the last one carries the MRF epilogue
+      const Act dst = last ? Act{} : ln.act((m & 1) ? Tb : R);
+      rc = run_conv(ln, L1, d, src, dst, ConvOpts().lrelu_in().residual(src.p),
+                    last ? &out : nullptr);
+      if (rc) return rc;
+      src = dst;
+      continue;
     }
+    // xt = lrelu(conv1(lrelu(x)))
+    const Act xt = ln.act(Tb);
+    if ((rc = run_conv(ln, L1, d, src, xt, ConvOpts().lrelu_in().lrelu_out()))) return rc;
+    // x = x + conv2(xt); the last one carries the MRF epilogue
+    const Act x = last ? Act{} : ln.act(R);
+    rc = run_conv(ln, h->layers[st.conv2[idx]], d, xt, x, ConvOpts().residual(src.p),
+                  last ? &out : nullptr);
     if (rc) return rc;
+    src = x;
   }
   return HFG_OK;
 }
-
-// Scratch of the concurrent-ResBlock schedule: per ResBlock its R / Tb and its output.
-struct RbConc {
-  float* R[HFG_MAX_RES];
-  float* Tb[HFG_MAX_RES];
-  float* O[HFG_MAX_RES];
-};
 
 // Aux streams of one batch part (created on first use; hipStreamNonBlocking)
 int rb_streams(hfg_handle* h, int part) {
@@ -493,21 +524,26 @@ int rb_streams(hfg_handle* h, int part) {
   return HFG_OK;
 }
 
+// The scratch of one MRF: seq for ResBlocks run one after another (or only_j alone), conc
+// (null: that schedule is off) one entry per ResBlock run side by side.
+struct MrfBufs {
+  const WsRbRegions& seq;
+  const WsRbRegions* conc = nullptr;
+};
+
 // MRF of stage st (models/hifigan.py:116-131) on X [B][C][L]: out = mean_j ResBlock_j(X)
-// (ResBlock.forward :72-86), or out = ResBlock_only_j(X) alone when only_j >= 0.  R and Tb
-// are B*C*L-float scratch buffers of the layer-per-launch ResBlocks; out must not alias X.
-// With conc set, the ResBlocks run concurrently (ResBlock j > 0 on aux stream j-1 of this
-// batch part), each into its own output, and one combine launch forms the mean in the
-// sequential schedule's order — bitwise the same result, for grids that leave CUs idle.
-// ax: f16x3 scale slot of X; aout: slot of out (the MRF mean, or ResBlock only_j's output)
-int run_mrf(hfg_handle* h, Launcher& ln, const Stage& st, const float* X, int64_t B, int64_t L,
-            float* R, float* Tb, float* out, const int32_t* lens, int only_j,
-            const uint32_t* ax, uint32_t* aout, const RbConc* conc = nullptr,
-            const PostFuse* post = nullptr) {
+// (ResBlock.forward :72-86), or out = ResBlock_only_j(X) alone when only_j >= 0; out must not
+// alias X.  With bufs.conc set, the ResBlocks run concurrently (ResBlock j > 0 on aux stream
+// j-1 of this batch part), each into its own output, and one combine launch forms the mean in
+// the sequential schedule's order — bitwise the same result, for grids that leave CUs idle.
+// post: conv_post + tanh in the last ResBlock's launch (sequential schedule only).
+int run_mrf(Launcher& ln, const Stage& st, const Dims& d, Src X, const MrfBufs& bufs, Act out,
+            int only_j, const PostFuse* post = nullptr) {
+  hfg_handle* h = ln.h;
   const hfg_config& c = h->cfg;
-  if (st.thin) return run_thin(h, ln, st, X, B, L, out, lens, only_j, aout);
+  if (st.thin) return run_thin(ln, st, d, X.p, out, only_j);
   int rc;
-  if (conc && only_j < 0 && c.n_res > 1) {
+  if (bufs.conc && only_j < 0 && c.n_res > 1) {
     if ((rc = rb_streams(h, ln.part))) return rc;
     hipError_t e = hipEventRecord(h->rb_fork[ln.part], ln.stream);
     for (int j = 1; j < c.n_res && e == hipSuccess; ++j)
@@ -520,49 +556,43 @@ int run_mrf(hfg_handle* h, Launcher& ln, const Stage& st, const float* X, int64_
     int j_main = 0;
     for (int j = 1; j < c.n_res; ++j)
       if (c.res_kernels[j] * c.n_dil[j] > c.res_kernels[j_main] * c.n_dil[j_main]) j_main = j;
-    int idx = 0;
+    hfg::MrfCombineArgs a{};
     for (int j = 0, aux = 0; j < c.n_res; ++j) {
-      Launcher lj{h, j == j_main ? ln.stream : h->rb_aux[ln.part][aux++], ln.part, ln.seq,
+      Launcher lj{h, ln.ws, j == j_main ? ln.stream : h->rb_aux[ln.part][aux++], ln.part, ln.seq,
                   c.n_res, ln.sl};
-      rc = run_one_rb(h, lj, st, j, idx, X, B, L, conc->R[j], conc->Tb[j], conc->O[j], 0, lens,
-                      ax, nullptr);
-      if (rc) return rc;
+      // mode 0: a plain store of the block's result
+      const MrfOut own{ln.at<float>(bufs.conc[j].out), 0, (float)c.n_res};
+      if ((rc = run_one_rb(lj, st, j, d, X, bufs.conc[j], own))) return rc;
       ln.seq = lj.seq;
-      idx += c.n_dil[j];
+      a.o[j] = own.y;
     }
     for (int j = 1; j < c.n_res && e == hipSuccess; ++j) {
       e = hipEventRecord(h->rb_join[ln.part][j - 1], h->rb_aux[ln.part][j - 1]);
       if (e == hipSuccess) e = hipStreamWaitEvent(ln.stream, h->rb_join[ln.part][j - 1], 0);
     }
     if (e != hipSuccess) return hip_fail(e, "ResBlock join");
-    hfg::MrfCombineArgs a{};
-    for (int j = 0; j < c.n_res; ++j) a.o[j] = conc->O[j];
     a.n = c.n_res;
     a.C = st.C;
-    a.L = (int)L;
-    a.len = lens;
-    a.y = out;
+    a.L = (int)d.L;
+    a.len = d.lens;
+    a.y = out.p;
     a.div = (float)c.n_res;
-    a.amax_out = aout;
-    ln.begin(0.0, 4.0 * B * L * st.C * (c.n_res + 1));
-    e = hfg::launch_mrf_combine(a, (int)B, ln.stream);
+    a.amax_out = out.amax;
+    ln.begin(0.0, 4.0 * d.B * d.L * st.C * (c.n_res + 1));
+    e = hfg::launch_mrf_combine(a, (int)d.B, ln.stream);
     ln.end("mrf_combine");
     if (e != hipSuccess) return hip_fail(e, "launch mrf_combine");
     return HFG_OK;
   }
-  int idx = 0;
   for (int j = 0; j < c.n_res; ++j) {
-    if (only_j >= 0 && j != only_j) {
-      idx += c.n_dil[j];
-      continue;
-    }
-    const int mode = only_j >= 0 ? 0 : ((j > 0 ? 1 : 0) | (j == c.n_res - 1 ? 2 : 0));
-    // the write that completes out: the last ResBlock's (the divide), or only_j's
-    rc = run_one_rb(h, ln, st, j, idx, X, B, L, R, Tb, out, mode, lens, ax,
-                    (only_j >= 0 || (mode & 2)) ? aout : nullptr,
-                    only_j < 0 && j == c.n_res - 1 ? post : nullptr);
-    if (rc) return rc;
-    idx += c.n_dil[j];
+    if (only_j >= 0 && j != only_j) continue;
+    const bool last = j == c.n_res - 1;
+    const int mode = only_j >= 0 ? 0 : ((j > 0 ? 1 : 0) | (last ? 2 : 0));
+    // the slot goes with the write that completes out: the last ResBlock's (the divide), or
+    // only_j's; conv_post with the last ResBlock's
+    const MrfOut to{out.p, mode, (float)c.n_res, only_j >= 0 || last ? out.amax : nullptr,
+                    only_j < 0 && last ? post : nullptr};
+    if ((rc = run_one_rb(ln, st, j, d, X, bufs.seq, to))) return rc;
   }
   return HFG_OK;
 }
@@ -575,52 +605,49 @@ bool post_fusable(const Stage& st, int64_t L, bool conc_st, float* const* taps) 
   return st.rbs.back().post && !taps && !conc_st && L % 4 == 0;
 }
 
-// taps (inspection, hfg_forward_taps): taps[0] <- conv_pre output, taps[1 + 2i] <- ups[i]
-// output, taps[2 + 2i] <- mrfs[i] output (models/hifigan.py:238-251); NULL entries skipped.
-int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hfg_forward_opts* o,
-                 float* wav, int64_t out_len, void* ws, size_t ws_len, hipStream_t stream,
-                 int part = 0, float* const* taps = nullptr, bool conc_ok = false) {
-  if (!mel || !wav) return fail(HFG_EINVAL, "mel / wav pointer is NULL");
-  const bool btc = o && o->mel_layout == HFG_MEL_BTC;
+// What every generator forward checks before it touches the workspace; *sh <- the shapes.
+int check_forward(const hfg_handle* h, const FwdIo& io, Shapes* sh) {
+  if (!io.mel || !io.wav) return fail(HFG_EINVAL, "mel / wav pointer is NULL");
+  const hfg_forward_opts* o = io.opts;
   if (o && o->mel_layout != HFG_MEL_BCT && o->mel_layout != HFG_MEL_BTC)
     return fail(HFG_EINVAL, "unknown mel_layout %d", o->mel_layout);
-  const int32_t* user_lens = o ? o->lengths : nullptr;
-  if (B <= 0 || T <= 0) return fail(HFG_EINVAL, "B and T must be > 0 (got %lld, %lld)",
-                                    (long long)B, (long long)T);
-  const Shapes sh = shapes_for(h, B, T);
-  for (auto l : sh.L)
-    if (l <= 0) return fail(HFG_EINVAL, "T=%lld gives an empty stage", (long long)T);
-  if (sh.L.back() != out_len)
-    return fail(HFG_EINVAL, "out_len %lld != expected %lld", (long long)out_len,
-                (long long)sh.L.back());
+  if (io.B <= 0 || io.T <= 0) return fail(HFG_EINVAL, "B and T must be > 0 (got %lld, %lld)",
+                                          (long long)io.B, (long long)io.T);
+  *sh = shapes_for(h, io.T);
+  for (auto l : sh->L)
+    if (l <= 0) return fail(HFG_EINVAL, "T=%lld gives an empty stage", (long long)io.T);
+  if (sh->L.back() != io.out_len)
+    return fail(HFG_EINVAL, "out_len %lld != expected %lld", (long long)io.out_len,
+                (long long)sh->L.back());
   // the kernels address one utterance's activations with 32-bit byte offsets from a
   // per-item base, through buffer descriptors of num_records 0xFFFFFFFF.  The hardware
   // drops a dword whose END passes num_records, so a 4 GiB item would lose its last
   // float: an item holds fewer than 2^30 fp32 elements (V1: T <= 131071 frames)
-  if (sh.item_elems >= ((int64_t)1 << 30))
+  if (sh->item_elems >= ((int64_t)1 << 30))
     return fail(HFG_EINVAL, "per-item activation of %lld elements reaches 2^30 (T too long)",
-                (long long)sh.item_elems);
-  if (ws_len < ws_part_bytes(h, B, T, conc_ok)) return fail(HFG_EINVAL, "workspace too small");
-  const int nb = n_bufs(h, B, T, conc_ok);
-  float* buf[4 + 3 * HFG_MAX_RES];
-  for (int i = 0; i < nb; ++i) buf[i] = reinterpret_cast<float*>(ws) + (size_t)i * sh.buf_elems;
-  RbConc conc{};
-  for (int j = 0; nb > 4 && j < h->cfg.n_res; ++j) {
-    conc.R[j] = buf[4 + 3 * j];
-    conc.Tb[j] = buf[5 + 3 * j];
-    conc.O[j] = buf[6 + 3 * j];
-  }
-  float* X = buf[0];    // upsampled stage input
-  float* R = buf[1];    // running ResBlock state (also conv_pre output)
-  float* Tb = buf[2];   // conv1 output
-  float* MRF = buf[3];  // MRF accumulator
-  // after the activation buffers: the length table, then the scale slots (ws_part_bytes)
-  int32_t* table = reinterpret_cast<int32_t*>(reinterpret_cast<float*>(ws) + (size_t)nb * sh.buf_elems);
-  Slots sl;
-  Launcher ln{h, stream, part};
-  ln.sl = &sl;
+                (long long)sh->item_elems);
+  return HFG_OK;
+}
+
+// One part of a checked forward (items [part.b0, part.b0 + part.B) of io) on `stream`, every
+// buffer a region of `part`; L: the stage lengths (Shapes::L).
+// taps (inspection, hfg_forward_taps): taps[0] <- conv_pre output, taps[1 + 2i] <- ups[i]
+// output, taps[2 + 2i] <- mrfs[i] output (models/hifigan.py:238-251); NULL entries skipped.
+int forward_part(Launcher& ln, const FwdIo& io, const std::vector<int64_t>& L, const WsPart& part) {
+  hfg_handle* h = ln.h;
+  hipStream_t stream = ln.stream;
   const hfg_config& c = h->cfg;
-  int rc = sl.begin(h, reinterpret_cast<char*>(table) + lens_table_bytes(h, B), B, stream);
+  const int64_t B = part.B, T = io.T;
+  const bool btc = io.opts && io.opts->mel_layout == HFG_MEL_BTC;
+  const int32_t* user_lens = io.opts && io.opts->lengths ? io.opts->lengths + part.b0 : nullptr;
+  const float* mel = io.mel + (size_t)part.b0 * c.n_mels * T;
+  float* wav = io.wav + (size_t)part.b0 * io.out_len;
+  float* const* taps = io.taps;
+  MrfBufs bufs{part.rb};  // (part.rb.out: the MRF accumulator)
+  int32_t* table = ln.at<int32_t>(part.table);
+  Slots sl;
+  ln.sl = &sl;
+  int rc = sl.begin(h, ln.at<uint32_t>(part.slots), part, stream);
   if (rc) return rc;
   // ragged batch: per-stage valid lengths, computed on the device from lengths[B]
   const int32_t* lt = nullptr;  // lt + s*B = lengths after s upsample stages
@@ -636,7 +663,8 @@ int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hf
     if (e != hipSuccess) return fail(HFG_EIO, "launch stage_lengths: %s", hipGetErrorString(e));
     lt = table;
   }
-  auto lens_at = [&](int s) { return lt ? lt + (size_t)s * B : nullptr; };
+  // stage s of this part: L[s] long, its row of the length table
+  auto dims = [&](int s) { return Dims{B, L[s], lt ? lt + (size_t)s * B : nullptr}; };
   auto tap = [&](int k, const float* src, int64_t n) -> int {
     if (!taps || !taps[k]) return HFG_OK;
     hipError_t e = hipMemcpyAsync(taps[k], src, sizeof(float) * (size_t)n,
@@ -644,60 +672,54 @@ int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hf
     return e == hipSuccess ? HFG_OK : hip_fail(e, "hipMemcpyAsync(tap)");
   };
   // f16x3: the mel's per-item max |value| (no kernel produced it)
-  uint32_t* a_mel = ln.take();
-  if (a_mel) {
+  const Src m = ln.act(mel);
+  if (m.amax) {
     ln.begin(0.0, 4.0 * B * c.n_mels * T);
     hipError_t e = hfg::launch_absmax(mel, (int64_t)c.n_mels * T, btc ? 1 : T, btc ? c.n_mels : 1,
-                                      c.n_mels, (int)T, lens_at(0), (int)B, a_mel, stream);
+                                      c.n_mels, (int)T, dims(0).lens, (int)B, m.amax, stream);
     ln.end("absmax");
     if (e != hipSuccess) return fail(HFG_EIO, "launch absmax: %s", hipGetErrorString(e));
   }
-  // conv_pre  (models/hifigan.py:238)
-  uint32_t* a_cur = ln.take();
-  rc = run_conv(h, ln, h->layers[h->conv_pre], mel, B, T, R, false, false, nullptr, nullptr, 0,
-                1.f, lens_at(0), a_mel, a_cur, btc);
+  // conv_pre  (models/hifigan.py:238), into R
+  Act cur = ln.act(ln.at<float>(part.rb.R));
+  rc = run_conv(ln, h->layers[h->conv_pre], dims(0), m, cur, ConvOpts().btc_input(btc));
   if (rc) return rc;
-  if ((rc = tap(0, R, B * c.c0 * T))) return rc;
+  if ((rc = tap(0, cur.p, B * c.c0 * T))) return rc;
   const Layer& Lp = h->layers[h->conv_post];
-  const float* cur = R;
   for (int i = 0; i < c.n_up; ++i) {
     const Stage& st = h->stages[i];
-    const int64_t Lin = sh.L[i], L = sh.L[i + 1];
+    const Dims d = dims(i + 1);
     // lrelu -> ups[i]  (models/hifigan.py:244-245)
-    uint32_t* a_x = ln.take();
-    rc = run_ups(h, ln, h->layers[st.conv_ups], cur, B, Lin, L, X, lens_at(i), lens_at(i + 1),
-                 a_cur, a_x);
-    if (rc) return rc;
-    if ((rc = tap(1 + 2 * i, X, B * st.C * L))) return rc;
+    const Act x = ln.act(ln.at<float>(part.X));
+    if ((rc = run_ups(ln, h->layers[st.conv_ups], dims(i), cur, d, x))) return rc;
+    if ((rc = tap(1 + 2 * i, x.p, B * st.C * d.L))) return rc;
     // MRF (models/hifigan.py:116-131) of ResBlocks (:72-86)
-    a_cur = ln.take();
-    const bool conc_st = nb > 4 && stage_conc(h, st, B, L);
-    if (i == c.n_up - 1 && post_fusable(st, L, conc_st, taps)) {
+    cur = ln.act(ln.at<float>(part.rb.out));
+    const bool conc_st = part.conc && stage_conc(h, st, B, d.L);
+    bufs.conc = conc_st ? part.rb_conc : nullptr;
+    if (i == c.n_up - 1 && post_fusable(st, d.L, conc_st, taps)) {
       // the last ResBlock's launch also runs lrelu -> conv_post -> tanh (models/hifigan.py:
       // 254-256); windows past an item's length write nothing: zero the wav first
       if (user_lens) {
-        hipError_t e = hipMemsetAsync(wav, 0, sizeof(float) * (size_t)(B * L), stream);
+        hipError_t e = hipMemsetAsync(wav, 0, sizeof(float) * (size_t)(B * d.L), stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(wav)");
       }
       const PostFuse pf{h->packed_dev + Lp.pk[0].w_off, h->packed_dev + Lp.pk[0].b_off, wav,
                         post_slope_of(h)};
-      rc = run_mrf(h, ln, st, X, B, L, R, Tb, MRF, lens_at(i + 1), -1, a_x, a_cur, nullptr, &pf);
+      rc = run_mrf(ln, st, d, x, bufs, cur, -1, &pf);
       return rc ? rc : sl.end();
     }
-    rc = run_mrf(h, ln, st, X, B, L, R, Tb, MRF, lens_at(i + 1), -1, a_x, a_cur,
-                 conc_st ? &conc : nullptr);
-    if (rc) return rc;
-    if ((rc = tap(2 + 2 * i, MRF, B * st.C * L))) return rc;
-    cur = MRF;
+    if ((rc = run_mrf(ln, st, d, x, bufs, cur, -1))) return rc;
+    if ((rc = tap(2 + 2 * i, cur.p, B * st.C * d.L))) return rc;
   }
   if ((rc = sl.end())) return rc;
   // lrelu -> conv_post -> tanh  (models/hifigan.py:254-256)
-  const int64_t L = sh.L.back();
+  const Dims d = dims(c.n_up);
   const char* name = nullptr;
-  ln.begin(2.0 * Lp.C_in * 7 * (double)L * B, 4.0 * B * L * (Lp.C_in + 1));
-  hipError_t e = hfg::launch_conv_post(cur, (int64_t)Lp.C_in * L, Lp.C_in, (int)L,
+  ln.begin(2.0 * Lp.C_in * 7 * (double)d.L * B, 4.0 * B * d.L * (Lp.C_in + 1));
+  hipError_t e = hfg::launch_conv_post(cur.p, (int64_t)Lp.C_in * d.L, Lp.C_in, (int)d.L,
                                        h->packed_dev + Lp.pk[0].w_off,
-                                       h->packed_dev + Lp.pk[0].b_off, wav, lens_at(c.n_up),
+                                       h->packed_dev + Lp.pk[0].b_off, wav, d.lens,
                                        post_slope_of(h), (int)B, stream, &name);
   ln.end(name);
   if (e != hipSuccess) return fail(HFG_EIO, "launch conv_post: %s", hipGetErrorString(e));
@@ -706,75 +728,61 @@ int forward_impl(hfg_handle* h, const float* mel, int64_t B, int64_t T, const hf
 
 }  // namespace
 
-// The forward of a batch: utterances are independent, so a batch of B >= 2 runs as two
-// halves on the caller's stream and an internal one (fork / join by events), each half
-// with its own workspace slice.  Each wav is bitwise the same as in a one-stream run.
-int forward_split(hfg_handle* h, const float* mel, int64_t B, int64_t T,
-                  const hfg_forward_opts* o, float* wav, int64_t out_len, void* ws, size_t ws_len,
-                  hipStream_t stream) {
+// A checked forward over its layout: one part on the caller's stream, or (utterances are
+// independent) two batch halves on the caller's stream and an internal one, fork / join by
+// events, each half with its own part of the workspace.  Each wav is bitwise the same as in a
+// one-stream run.
+int forward_run(hfg_handle* h, const FwdIo& io, void* ws, size_t ws_len, hipStream_t stream,
+                bool taps) {
   ++h->fwd_count;
-  h->halves = split_batch(h, B, T) ? 2 : 1;
-  if (h->halves == 1)
-    return forward_impl(h, mel, B, T, o, wav, out_len, ws, ws_len, stream, 0, nullptr, true);
-  if (B <= 0 || T <= 0) return fail(HFG_EINVAL, "B and T must be > 0");
-  if (ws_len < ws_bytes_for(h, B, T)) return fail(HFG_EINVAL, "workspace too small");
+  Shapes sh;
+  int rc = check_forward(h, io, &sh);
+  if (rc) return rc;
+  const WsLayout lay = ws_layout(h, io.B, io.T, taps);
+  if (ws_len < lay.total) return fail(HFG_EINVAL, "workspace too small");
+  h->halves = lay.n_parts;
+  Launcher l0{h, ws, stream, 0};
+  if (lay.n_parts == 1) return forward_part(l0, io, sh.L, lay.part[0]);
   if (!h->aux) {
     hipError_t e = hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->join_ev, hipEventDisableTiming);
     if (e != hipSuccess) return hip_fail(e, "create split stream");
   }
-  const int64_t B1 = (B + 1) / 2, B2 = B - B1;
-  const size_t w1 = ws_part_bytes(h, B1, T);
-  hipStream_t s0 = stream, s1 = h->aux;
   hipError_t e = hipEventRecord(h->fork_ev, stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(s1, h->fork_ev, 0);
+  if (e == hipSuccess) e = hipStreamWaitEvent(h->aux, h->fork_ev, 0);
   if (e != hipSuccess) return hip_fail(e, "fork");
-  int rc = forward_impl(h, mel, B1, T, o, wav, out_len, ws, w1, s0, 0);
-  if (rc) return rc;
-  hfg_forward_opts o2{};
-  if (o) {
-    o2 = *o;
-    if (o->lengths) o2.lengths = o->lengths + B1;
-  }
-  rc = forward_impl(h, mel + (size_t)B1 * h->cfg.n_mels * T, B2, T, o ? &o2 : nullptr,
-                    wav + (size_t)B1 * out_len, out_len, static_cast<char*>(ws) + w1,
-                    ws_len - w1, s1, 1);
-  e = hipEventRecord(h->join_ev, s1);
+  if ((rc = forward_part(l0, io, sh.L, lay.part[0]))) return rc;
+  Launcher l1{h, ws, h->aux, 1};
+  rc = forward_part(l1, io, sh.L, lay.part[1]);
+  e = hipEventRecord(h->join_ev, h->aux);
   if (e == hipSuccess) e = hipStreamWaitEvent(stream, h->join_ev, 0);
   if (e != hipSuccess) return hip_fail(e, "join");
   return rc;
 }
 
-int forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, float* wav,
-                 int64_t out_len, void* ws, size_t ws_len, float* const* taps, hipStream_t stream) {
-  ++h->fwd_count;
-  h->halves = 1;
-  return forward_impl(h, mel, B, T, nullptr, wav, out_len, ws, ws_len, stream, 0, taps,
-                      !split_batch(h, B, T));
-}
-
 // ---- one MRF / one ResBlock (MRF-only handles, hfg_mrf_create) ---------------
-int mrf_run(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, float* y, void* ws,
-            size_t ws_bytes, hipStream_t st) {
+int mrf_run(hfg_handle* h, int only_j, const float* x_in, int64_t L, float* y, const WsPart& part,
+            void* ws, hipStream_t st) {
   ++h->fwd_count;
   h->halves = 1;
   const int C = h->stages[0].C;
-  const size_t one = (mrf_ws_bytes(h, B, L) - slots_bytes(h, B)) / 2;
-  float* R = static_cast<float*>(ws);
-  float* Tb = R + one / sizeof(float);
+  const int64_t B = part.B;
   Slots sl;
-  Launcher ln{h, st, 0};
+  Launcher ln{h, ws, st, 0};
   ln.sl = &sl;
-  int rc = sl.begin(h, static_cast<char*>(ws) + 2 * one, B, st);
+  int rc = sl.begin(h, ln.at<uint32_t>(part.slots), part, st);
   if (rc) return rc;
   // f16x3: the caller's x, its per-item max |value| by an absmax pass
-  uint32_t* ax = ln.take();
-  if (ax) {
-    hipError_t e = hfg::launch_absmax(x, (int64_t)C * L, L, 1, C, (int)L, nullptr, (int)B, ax, st);
+  const Src x = ln.act(x_in);
+  if (x.amax) {
+    hipError_t e =
+        hfg::launch_absmax(x.p, (int64_t)C * L, L, 1, C, (int)L, nullptr, (int)B, x.amax, st);
     if (e != hipSuccess) return fail(HFG_EIO, "launch absmax: %s", hipGetErrorString(e));
   }
-  rc = run_mrf(h, ln, h->stages[0], x, B, L, R, Tb, y, nullptr, only_j, ax, nullptr);
+  // (no consumer of y's scale)
+  rc = run_mrf(ln, h->stages[0], Dims{B, L, nullptr}, x, MrfBufs{part.rb}, Act{y, nullptr},
+               only_j);
   return rc ? rc : sl.end();
 }
 

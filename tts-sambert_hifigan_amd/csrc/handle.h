@@ -183,6 +183,12 @@ struct hfg_handle {
   int split = 2;
   static constexpr int64_t kSplitMinFrames = 4096;  // batch frames from which a forward runs as
                                                     // two halves on two streams
+  // concurrent ResBlocks for a stage whose grids leave CUs idle: fewer tile-3 blocks (128 rows
+  // x 256 columns) per conv than this.  512 (the chip's tile-3 slots) until round 6; with the
+  // cheaper mrf_combine, 2048 also takes the whole-ResBlock stages of mid-size single-stream
+  // forwards (same-box sweep, profiles/r06/c1/c1_ab_cb.txt: 4 x 512 frames -3.7 %, 32 x 62
+  // -1.6 %, 1 x 4096 -0.8 %, 1 x 8192 and 16 x 256 unchanged; 4096 cost 1 x 8192 +1.2 %)
+  static constexpr int64_t kConcBlocks = 2048;
   hipStream_t aux = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   // concurrent ResBlocks of small forwards (RB_CONC: -1 auto, 0 off, 1 whenever the
@@ -207,19 +213,51 @@ int plan_handle(hfg_handle* h);
 
 struct Shapes {
   std::vector<int64_t> L;  // L[0] = T, L[i+1] = length after stage i
-  int64_t buf_elems;       // per-buffer elements (all B items)
   int64_t item_elems;      // largest per-item activation (max over stages of C * L)
 };
-Shapes shapes_for(const hfg_handle* h, int64_t B, int64_t T);
-size_t lens_table_bytes(const hfg_handle* h, int64_t B);
+Shapes shapes_for(const hfg_handle* h, int64_t T);
 bool stage_conc(const hfg_handle* h, const Stage& st, int64_t B, int64_t L);
-int n_bufs(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok);
-int n_slots(const hfg_handle* h);
-size_t slots_bytes(const hfg_handle* h, int64_t B);
-size_t ws_part_bytes(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok = false);
 bool split_batch(const hfg_handle* h, int64_t B, int64_t T);
+
+// The workspace of a forward, stated once: plan.cpp computes it, the public sizes
+// (hfg_workspace_bytes, hfg_mrf_workspace_bytes, hfg_reserve) are its totals, forward.cpp
+// takes every pointer from it and hfg_debug_workspace prints it.  Offsets are bytes from the
+// workspace's start, every region 256-byte aligned; bytes == 0: the region is absent.
+struct WsRegion { size_t off = 0, bytes = 0; };
+// R / Tb of a layer-per-launch ResBlock (Tb: also a split whole-ResBlock launch's x), and
+// with concurrent ResBlocks the block's own output
+struct WsRbRegions { WsRegion R, Tb, out; };
+// One forward part: batch items [b0, b0 + B) on one stream.
+struct WsPart {
+  int64_t b0 = 0, B = 0;
+  size_t off = 0, bytes = 0;
+  WsRegion X;               // upsampled stage input
+  WsRbRegions rb;           // R: running ResBlock state (also conv_pre output); rb.out: the
+                            // MRF accumulator (absent in an MRF-only forward, which writes y)
+  bool conc = false;        // some stage runs concurrent ResBlocks: rb_conc[0, n_res) present
+  WsRbRegions rb_conc[HFG_MAX_RES];
+  WsRegion table;           // per-stage valid lengths of a ragged batch, [n_up + 1][B] int32
+  WsRegion slots;           // f16x3 scale slots, [n_slots][B][kAmaxSlotWords] uint32
+};
+struct WsLayout {
+  int n_parts = 1;          // 2: the batch halves of a split forward, each on its stream
+  WsPart part[2];
+  size_t total = 0;
+};
+// A generator forward.  taps: hfg_forward_taps' one-stream forward, the whole batch as one
+// part (with concurrent ResBlocks only where the split forward is one part too).
+WsLayout ws_layout(const hfg_handle* h, int64_t B, int64_t T, bool taps);
+// What hfg_workspace_bytes promises: room for either layout above.
 size_t ws_bytes_for(const hfg_handle* h, int64_t B, int64_t T);
-size_t mrf_ws_bytes(const hfg_handle* h, int64_t B, int64_t L);
+// An MRF-only forward: one part of rb.R, rb.Tb and the slots.
+WsLayout mrf_ws_layout(const hfg_handle* h, int64_t B, int64_t L);
+// f16x3 scale slots of one forward part: one [B] row of per-item max |value| per launch that
+// commits a scale, handed out in launch order (forward.cpp, Launcher::act).  Those launches:
+// the absmax pass over the caller's mel (or an MRF-only forward's x), conv_pre, every
+// upsampler, every MRF output, and in a layer-by-layer ResBlock every conv but its last
+// (whose output is the MRF write).  Fewer than layers + 2 n_up + 4 in every schedule; a
+// schedule that asks for more fails with "scale slots exhausted".
+int n_slots(const hfg_handle* h);
 
 // ---- pack.cpp ---------------------------------------------------------------
 // Every weight set -> h->packed_host (HFG_EAGAIN while one is missing); sets Layer::ew.
@@ -240,13 +278,24 @@ struct ForwardScope {
     return h->dirty ? do_commit(h) : HFG_OK;
   }
 };
-int forward_split(hfg_handle* h, const float* mel, int64_t B, int64_t T,
-                  const hfg_forward_opts* o, float* wav, int64_t out_len, void* ws, size_t ws_len,
-                  hipStream_t stream);
-// one stream, with the inspection taps of hfg_forward_taps
-int forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, float* wav,
-                 int64_t out_len, void* ws, size_t ws_len, float* const* taps, hipStream_t stream);
-int mrf_run(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, float* y, void* ws,
-            size_t ws_bytes, hipStream_t stream);
+// What the caller of a generator forward passed: mel [B][n_mels][T] (or BTC, opts) -> wav
+// [B][out_len]; taps: hfg_forward_taps' stage-output copies (may be NULL there too).
+struct FwdIo {
+  const float* mel;
+  int64_t B, T;
+  const hfg_forward_opts* opts;
+  float* wav;
+  int64_t out_len;
+  float* const* taps;
+};
+// Checks the arguments, lays the caller's workspace out (ws_layout) and refuses one smaller
+// than that layout's total.  The batch halves run on two streams where split_batch says so;
+// taps: hfg_forward_taps' forward, one stream.
+int forward_run(hfg_handle* h, const FwdIo& io, void* ws, size_t ws_len, hipStream_t stream,
+                bool taps);
+// An MRF-only forward: x [part.B][C][L] -> y, the whole MRF (only_j < 0) or ResBlock only_j;
+// ws: at least the total of the mrf_ws_layout that `part` is the one part of.
+int mrf_run(hfg_handle* h, int only_j, const float* x, int64_t L, float* y, const WsPart& part,
+            void* ws, hipStream_t stream);
 
 }  // namespace hfg_host

@@ -346,7 +346,7 @@ int hfg_commit_weights(hfg_handle* h) {
 
 int64_t hfg_out_len(const hfg_handle* h, int64_t T) {
   if (!h || T <= 0 || h->mrf_only) return -1;
-  return shapes_for(h, 1, T).L.back();
+  return shapes_for(h, T).L.back();
 }
 
 size_t hfg_workspace_bytes(const hfg_handle* h, int64_t B, int64_t T) {
@@ -385,8 +385,8 @@ int hfg_forward_ex(hfg_handle* h, const float* mel, int64_t B, int64_t T,
   ForwardScope scope(h);
   if (!workspace) return fail(HFG_EINVAL, "workspace is NULL");
   if ((rc = scope.ready(h))) return rc;
-  return forward_split(h, mel, B, T, opts, wav, out_len, workspace, workspace_bytes,
-                       reinterpret_cast<hipStream_t>(stream));
+  return forward_run(h, FwdIo{mel, B, T, opts, wav, out_len, nullptr}, workspace, workspace_bytes,
+                     reinterpret_cast<hipStream_t>(stream), false);
 }
 
 int hfg_forward_ws(hfg_handle* h, const float* mel, int64_t B, int64_t T, float* wav,
@@ -416,16 +416,17 @@ int mrf_entry(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, f
   if ((int64_t)h->stages[0].C * L >= ((int64_t)1 << 30))
     return fail(HFG_EINVAL, "per-item activation reaches 2^30 elements");
   ForwardScope scope(h);
-  if (ws_bytes < mrf_ws_bytes(h, B, L)) return fail(HFG_EINVAL, "workspace too small");
+  const WsLayout lay = mrf_ws_layout(h, B, L);
+  if (ws_bytes < lay.total) return fail(HFG_EINVAL, "workspace too small");
   int rc = scope.ready(h);
   if (rc) return rc;
-  return mrf_run(h, only_j, x, B, L, y, ws, ws_bytes, reinterpret_cast<hipStream_t>(stream));
+  return mrf_run(h, only_j, x, L, y, lay.part[0], ws, reinterpret_cast<hipStream_t>(stream));
 }
 }  // namespace
 
 size_t hfg_mrf_workspace_bytes(const hfg_handle* h, int64_t B, int64_t L) {
   if (!h || !h->mrf_only || B <= 0 || L <= 0) return 0;
-  return mrf_ws_bytes(h, B, L);
+  return mrf_ws_layout(h, B, L).total;
 }
 
 int hfg_mrf_forward(hfg_handle* h, const float* x, int64_t B, int64_t L, float* y,
@@ -702,6 +703,43 @@ int64_t hfg_debug_lds_bytes(const char* family, const int* a, int n) {
   return -1;
 }
 
+// The workspace layout of a forward (handle.h, WsLayout) as JSON: what the public sizes total
+// and the schedule carves, for the host suite (tests/test_workspace_layout_host.py).
+int hfg_debug_workspace(const hfg_handle* h, int64_t B, int64_t T_or_L, int taps, char* buf,
+                        size_t buflen) {
+  if (!h || !buf || buflen == 0) return fail(HFG_EINVAL, "bad arguments");
+  if (B <= 0 || T_or_L <= 0) return fail(HFG_EINVAL, "B and T (L) must be > 0");
+  const WsLayout lay = h->mrf_only ? mrf_ws_layout(h, B, T_or_L) : ws_layout(h, B, T_or_L, taps != 0);
+  std::string s = "{\"total\": " + std::to_string(lay.total) + ", \"parts\": [";
+  for (int q = 0; q < lay.n_parts; ++q) {
+    const WsPart& p = lay.part[q];
+    s += std::string(q ? ", " : "") + "{\"b0\": " + std::to_string(p.b0) + ", \"B\": " +
+         std::to_string(p.B) + ", \"off\": " + std::to_string(p.off) + ", \"bytes\": " +
+         std::to_string(p.bytes) + ", \"regions\": [";
+    bool first = true;
+    auto region = [&](const std::string& name, const WsRegion& r) {
+      s += std::string(first ? "" : ", ") + "{\"name\": \"" + name + "\", \"off\": " +
+           std::to_string(r.off) + ", \"bytes\": " + std::to_string(r.bytes) + "}";
+      first = false;
+    };
+    if (!h->mrf_only) region("X", p.X);
+    region("R", p.rb.R), region("Tb", p.rb.Tb);
+    if (!h->mrf_only) region("MRF", p.rb.out);
+    for (int j = 0; p.conc && j < h->cfg.n_res; ++j) {
+      const std::string rb = "rb" + std::to_string(j);
+      region(rb + ".R", p.rb_conc[j].R), region(rb + ".Tb", p.rb_conc[j].Tb);
+      region(rb + ".out", p.rb_conc[j].out);
+    }
+    if (!h->mrf_only) region("table", p.table);
+    region("slots", p.slots);
+    s += "]}";
+  }
+  s += "]}";
+  if (s.size() + 1 > buflen) return fail(HFG_EINVAL, "buffer too small (%zu needed)", s.size() + 1);
+  memcpy(buf, s.c_str(), s.size() + 1);
+  return HFG_OK;
+}
+
 // JSON description of everything the launch code reads from the plan (layers, whole-ResBlock
 // and thin-stage launches, packed-buffer offsets) and the sha256 of the packed image: the
 // fingerprint the host suite pins (tests/test_plan_host.py).  Commits pending weights first.
@@ -794,8 +832,8 @@ int hfg_forward_taps(hfg_handle* h, const float* mel, int64_t B, int64_t T, floa
   ForwardScope scope(h);
   int rc = scope.ready(h);
   if (rc) return rc;
-  return forward_taps(h, mel, B, T, wav, out_len, workspace, workspace_bytes, taps,
-                      reinterpret_cast<hipStream_t>(stream));
+  return forward_run(h, FwdIo{mel, B, T, nullptr, wav, out_len, taps}, workspace, workspace_bytes,
+                     reinterpret_cast<hipStream_t>(stream), true);
 }
 
 }  // extern "C"

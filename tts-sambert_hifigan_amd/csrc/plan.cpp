@@ -1,12 +1,13 @@
 // plan.cpp — what a handle decides before any weight or input arrives: the layer list in the
 // reference's order, each layer's kernel path, tile and packings, the whole-ResBlock and
 // thin-stage launches with their windows and halos, the packed-buffer offsets; and the
-// shapes, workspace and scale-slot sizes of a forward.  No HIP runtime call.
+// shapes and the workspace layout of a forward (handle.h, WsLayout).  No HIP runtime call.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
+#include <utility>
 
 #include "handle.h"
 
@@ -438,7 +439,7 @@ int plan_handle(hfg_handle* h) {
 }
 
 // ---- shape bookkeeping ------------------------------------------------------
-Shapes shapes_for(const hfg_handle* h, int64_t B, int64_t T) {
+Shapes shapes_for(const hfg_handle* h, int64_t T) {
   Shapes s;
   s.L.push_back(T);
   int64_t mx = (int64_t)h->cfg.c0 * T;
@@ -449,76 +450,87 @@ Shapes shapes_for(const hfg_handle* h, int64_t B, int64_t T) {
     mx = std::max(mx, (int64_t)(h->cfg.c0 >> (i + 1)) * std::max<int64_t>(lo, 0));
   }
   s.item_elems = mx;
-  s.buf_elems = ((mx * B + 63) / 64) * 64;
   return s;
 }
 
-namespace {
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-}  // namespace
-
-// the per-stage length table of a ragged batch
-size_t lens_table_bytes(const hfg_handle* h, int64_t B) {
-  return align256((size_t)(h->cfg.n_up + 1) * (size_t)B * sizeof(int32_t));
-}
-// concurrent ResBlocks for a stage whose grids leave CUs idle: fewer tile-3 blocks (128 rows
-// x 256 columns) per conv than HFG_CONC_BLOCKS.  512 (the chip's tile-3 slots) until round 6;
-// with the cheaper mrf_combine, 2048 also takes the whole-ResBlock stages of mid-size single-
-// stream forwards (same-box sweep, profiles/r06/c1/c1_ab_cb.txt: 4 x 512 frames -3.7 %,
-// 32 x 62 -1.6 %, 1 x 4096 -0.8 %, 1 x 8192 and 16 x 256 unchanged; 4096 cost 1 x 8192 +1.2 %)
-#ifndef HFG_CONC_BLOCKS
-#define HFG_CONC_BLOCKS 2048
-#endif
+// ---- the forward workspace (handle.h, WsLayout) ------------------------------
 bool stage_conc(const hfg_handle* h, const Stage& st, int64_t B, int64_t L) {
   const int n_res = h->cfg.n_res;
   if (h->rb_conc == 0 || st.thin || n_res < 2 || n_res > hfg::kMrfCombineMax) return false;
   if (h->rb_conc == 1) return true;
-  return B * ((L + 255) / 256) * ((st.C + 127) / 128) < HFG_CONC_BLOCKS;
-}
-namespace {
-bool any_conc(const hfg_handle* h, int64_t B, int64_t T) {
-  if (h->mrf_only) return false;
-  const Shapes sh = shapes_for(h, B, T);
-  for (size_t i = 0; i < h->stages.size(); ++i)
-    if (stage_conc(h, h->stages[i], B, sh.L[i + 1])) return true;
-  return false;
-}
-}  // namespace
-// activation buffers of one forward part: X, R, Tb, MRF, and with concurrent ResBlocks an
-// R / Tb / output triple per ResBlock
-int n_bufs(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok) {
-  return 4 + (conc_ok && any_conc(h, B, T) ? 3 * h->cfg.n_res : 0);
-}
-// f16x3 scale slots of one forward part: one [B] row of per-item max |value| per producing
-// launch (the mel's absmax, conv_pre, every upsampler, layer conv and MRF output), zeroed at
-// the start of the forward
-int n_slots(const hfg_handle* h) { return (int)h->layers.size() + 2 * h->cfg.n_up + 4; }
-size_t slots_bytes(const hfg_handle* h, int64_t B) {
-  if (h->fmt != hfg::kFmtF16) return 0;
-  return align256((size_t)n_slots(h) * (size_t)B * hfg::kAmaxSlotWords * sizeof(uint32_t));
-}
-// workspace of one forward part (one batch half): the activation buffers, the length table,
-// the scale slots
-size_t ws_part_bytes(const hfg_handle* h, int64_t B, int64_t T, bool conc_ok) {
-  return align256((size_t)n_bufs(h, B, T, conc_ok) * sizeof(float) *
-                      (size_t)shapes_for(h, B, T).buf_elems +
-                  lens_table_bytes(h, B) + slots_bytes(h, B));
+  return B * ((L + 255) / 256) * ((st.C + 127) / 128) < hfg_handle::kConcBlocks;
 }
 // small forwards stay on one stream: splitting them doubles an already latency-bound
 // launch count (measured: 32 x 62 frames 5.4 -> 5.6 ms split)
 bool split_batch(const hfg_handle* h, int64_t B, int64_t T) {
   return h->split >= 2 && B >= 2 && B * T >= hfg_handle::kSplitMinFrames;
 }
-// workspace of a forward: both halves' when the batch is split over two streams (whose
-// ResBlocks then run one after another), else one part with concurrent ResBlocks allowed
-size_t ws_bytes_for(const hfg_handle* h, int64_t B, int64_t T) {
-  if (!split_batch(h, B, T)) return ws_part_bytes(h, B, T, true);
-  const int64_t B1 = (B + 1) / 2;
-  return ws_part_bytes(h, B1, T) + ws_part_bytes(h, B - B1, T);
+int n_slots(const hfg_handle* h) { return (int)h->layers.size() + 2 * h->cfg.n_up + 4; }
+
+namespace {
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Regions one after another from the part's offset; every size a multiple of 256.
+struct WsBump {
+  size_t off;
+  WsRegion take(size_t n) { return {std::exchange(off, off + align256(n)), align256(n)}; }
+  WsRbRegions take_rb(size_t buf, bool out) { return {take(buf), take(buf), take(out ? buf : 0)}; }
+};
+// the scale slots are zeroed at the start of the forward; none in the unscaled modes
+size_t slots_bytes(const hfg_handle* h, int64_t B) {
+  if (h->fmt != hfg::kFmtF16) return 0;
+  return (size_t)n_slots(h) * (size_t)B * hfg::kAmaxSlotWords * sizeof(uint32_t);
 }
-// an MRF-only forward: R and Tb of the layer-per-launch ResBlocks, the scale slots
-size_t mrf_ws_bytes(const hfg_handle* h, int64_t B, int64_t L) {
-  return 2 * align256(sizeof(float) * (size_t)B * h->stages[0].C * (size_t)L) + slots_bytes(h, B);
+
+// One part of a generator forward at `off`: X, R, Tb, MRF, with concurrent ResBlocks an
+// R / Tb / output triple per ResBlock, the length table, the scale slots.
+WsPart part_layout(const hfg_handle* h, int64_t b0, int64_t B, int64_t T, bool conc, size_t off) {
+  const Shapes sh = shapes_for(h, T);
+  const size_t buf = sizeof(float) * (size_t)sh.item_elems * (size_t)B;  // one activation
+  WsPart p{b0, B, off};
+  WsBump at{off};
+  p.X = at.take(buf);
+  p.rb = at.take_rb(buf, true);
+  for (size_t i = 0; conc && i < h->stages.size(); ++i)
+    p.conc = p.conc || stage_conc(h, h->stages[i], B, sh.L[i + 1]);
+  for (int j = 0; p.conc && j < h->cfg.n_res; ++j) p.rb_conc[j] = at.take_rb(buf, true);
+  p.table = at.take((size_t)(h->cfg.n_up + 1) * (size_t)B * sizeof(int32_t));
+  p.slots = at.take(slots_bytes(h, B));
+  p.bytes = at.off - off;
+  return p;
+}
+}  // namespace
+
+// Both halves when the batch is split over two streams (whose ResBlocks then run one after
+// another), else one part with concurrent ResBlocks allowed.
+WsLayout ws_layout(const hfg_handle* h, int64_t B, int64_t T, bool taps) {
+  const bool split = split_batch(h, B, T);
+  const int64_t B1 = split && !taps ? (B + 1) / 2 : B;
+  WsLayout w;
+  w.part[0] = part_layout(h, 0, B1, T, !split, 0);
+  w.total = w.part[0].bytes;
+  if (B1 < B) {
+    w.n_parts = 2;
+    w.part[1] = part_layout(h, B1, B - B1, T, false, w.total);
+    w.total += w.part[1].bytes;
+  }
+  return w;
+}
+// (the taps layout never is the larger one, every term of a part being subadditive in B;
+// taking the max states that instead of relying on it)
+size_t ws_bytes_for(const hfg_handle* h, int64_t B, int64_t T) {
+  return std::max(ws_layout(h, B, T, false).total, ws_layout(h, B, T, true).total);
+}
+// R and Tb of the layer-per-launch ResBlocks ([B][C][L] each), the scale slots
+WsLayout mrf_ws_layout(const hfg_handle* h, int64_t B, int64_t L) {
+  WsLayout w;
+  WsPart& p = w.part[0];
+  p.B = B;
+  WsBump at{0};
+  p.rb = at.take_rb(sizeof(float) * (size_t)B * h->stages[0].C * (size_t)L, false);
+  p.slots = at.take(slots_bytes(h, B));
+  w.total = p.bytes = at.off;
+  return w;
 }
 
 }  // namespace hfg_host
