@@ -623,3 +623,29 @@ def test_schedule_ignores_environment(pkg, monkeypatch, sched):
     assert _fused_flag(pkg) == 0
     pkg.schedule_clear("FUSED_RB")
     assert _fused_flag(pkg) == 1
+
+
+@pytest.mark.parametrize("entry", ["hfg_debug_plan", "hfg_debug_workspace"])
+def test_text_entries_size_their_buffer(pkg, entry):
+    """A text-returning inspection entry refuses a buffer that is too small with HFG_EINVAL
+    and names the size N it needs (text + NUL); exactly N bytes hold the whole JSON, N - 1 do
+    not."""
+    import json
+    h = host_handle(pkg, C.V1)
+    if entry == "hfg_debug_plan":
+        for k, v in C.make_state_dict(C.V1, seed=0).items():
+            h.set_weight(k, torch.from_numpy(v))
+        call = lambda buf: h.lib.hfg_debug_plan(h.ptr, buf, len(buf))
+    else:
+        call = lambda buf: h.lib.hfg_debug_workspace(h.ptr, 8, 1024, 0, buf, len(buf))
+    assert call(ctypes.create_string_buffer(1)) == -22
+    m = re.search(r"buffer too small \((\d+) needed\)", h.lib.hfg_last_error().decode())
+    assert m, h.lib.hfg_last_error()
+    n = int(m.group(1))
+    assert n > 1
+    exact = ctypes.create_string_buffer(n)
+    assert call(exact) == 0
+    assert len(exact.value) == n - 1  # the NUL is the buffer's last byte
+    full = h.plan() if entry == "hfg_debug_plan" else h.workspace_layout(8, 1024)
+    assert json.loads(exact.value.decode()) == full
+    assert call(ctypes.create_string_buffer(n - 1)) == -22

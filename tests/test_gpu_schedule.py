@@ -124,3 +124,39 @@ def test_launches_match_fixture(pkg, index, name):
     assert sorted(got) == sorted(want), f"{name}: kernel instances differ"
     for label in want:
         assert got[label] == want[label], f"{name}: {label}: [launches, flop, bytes] differ"
+
+
+def test_profile_summary_sizes_its_buffer(pkg):
+    """hfg_profile_summary into a buffer of exactly the size its refusal names holds the
+    whole JSON: the labels and launch counts of a 64 KiB buffer's."""
+    import ctypes
+    import re
+    from oracle import config as C
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    dev = torch.device("cuda:0")
+    cfg = C.GenConfig(n_mels=16, upsample_rates=[2, 2], upsample_kernel_sizes=[4, 4],
+                      upsample_initial_channel=64, resblock_kernel_sizes=[3],
+                      resblock_dilation_sizes=[[1, 3]])
+    mod = pkg.HiFiGANGenerator(**cfg.kwargs(), precision="f16x3").eval()
+    mod.load_state_dict({k: torch.from_numpy(v) for k, v in C.make_state_dict(cfg, seed=7).items()})
+    mod = mod.to(dev)
+    h = mod._handle_for(dev)
+    h.profile_reset()
+    h.set_profiling(True)
+    with torch.no_grad():
+        mod(torch.randn(1, cfg.n_mels, 8, generator=torch.Generator().manual_seed(8)).to(dev))
+    torch.cuda.synchronize()
+    h.set_profiling(False)
+    big = h.profile_summary()  # a 64 KiB buffer
+    assert big and all(v["launches"] >= 1 for v in big.values())
+    assert h.lib.hfg_profile_summary(h.ptr, ctypes.create_string_buffer(1), 1) == -22
+    n = int(re.search(r"buffer too small \((\d+) needed\)",
+                      h.lib.hfg_last_error().decode()).group(1))
+    exact = ctypes.create_string_buffer(n)
+    assert h.lib.hfg_profile_summary(h.ptr, exact, n) == 0
+    got = json.loads(exact.value.decode())
+    assert len(exact.value) == n - 1
+    assert {k: v["launches"] for k, v in got.items()} == {k: v["launches"] for k, v in big.items()}
+    assert h.lib.hfg_profile_summary(h.ptr, ctypes.create_string_buffer(n - 1), n - 1) == -22
+    h.profile_reset()

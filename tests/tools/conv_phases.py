@@ -1,5 +1,7 @@
 """Phase times inside the tile-5 layer-conv kernel from the diagnostic build's clock stamps
 (conv_bf16x3.hip, -DHFG_CONV_TIMING=1; built as ab/cvts.so by profiles/r04/ab_build.sh).
+The buffer's shape comes from the library (hfg_debug_cv_ts_geometry); the slots are CvTsSlot
+of csrc/diag.h.
 
 GPU box:  python tests/tools/conv_phases.py LIB.so   (LIB.so = the package's library path,
 holding the diagnostic build).  Per KT (the last launch of that KT in a V1 [8, 80, 1024]
@@ -16,7 +18,16 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-SLOTS, BLOCKS, REGIONS = 16, 8192, 12
+# CvTsSlot (csrc/diag.h)
+START, SETUP, PROLOGUE, LOOP, END, BAR_WAIT, END_REAL, EPI_BARRIER, EPI_TILE, HW_ID = (
+    0, 1, 2, 3, 4, 5, 6, 7, 8, 12)
+
+
+def geometry(dl, tag):
+    """(slots, blocks, regions) of the library's stamp buffer (csrc/diag.h)."""
+    g = [ctypes.c_int() for _ in range(3)]
+    getattr(dl, f"hfg_debug_{tag}_ts_geometry")(*[ctypes.byref(v) for v in g])
+    return tuple(v.value for v in g)
 
 
 def main():
@@ -48,36 +59,38 @@ def main():
     assert dl.hfg_debug_cv_ts_clear() == 0
     h.forward_ws(mel.data_ptr(), B, T, wav.data_ptr(), out_len, ws.data_ptr(), ws_bytes, st)
     torch.cuda.synchronize(dev)
+    SLOTS, BLOCKS, REGIONS = geometry(dl, "cv")
+    assert SLOTS > HW_ID and REGIONS >= 12, "stamp layout older than this tool"
     buf = np.zeros(REGIONS * BLOCKS * SLOTS, dtype=np.uint64)
     assert dl.hfg_debug_cv_ts(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
     buf = buf.reshape(REGIONS, BLOCKS, SLOTS).astype(np.int64)
     odir = os.path.join(ROOT, "gpurun_out", "r05")
     os.makedirs(odir, exist_ok=True)
     tag = os.environ.get("CVP_TAG", "default")
-    # raw stamps (slot 12: HW_ID | XCC_ID << 32 of the block's wave 0) for offline analysis
+    # raw stamps (slot HW_ID: HW_ID | XCC_ID << 32 of the block's wave 0) for offline analysis
     np.save(os.path.join(odir, f"cvp_raw_{tag}.npy"), buf[:9])
     out = {}
     for r, (kt, epi) in enumerate((k, e) for k in (3, 7, 11, 0) for e in ("plain", "res", "res+mrf")):
         blk = buf[r]
-        blk = blk[(blk[:, 1] != 0) & (blk[:, 4] != 0)]
+        blk = blk[(blk[:, SETUP] != 0) & (blk[:, END] != 0)]
         if not len(blk):
             continue
-        tot = blk[:, 4] - blk[:, 1]
-        rt = np.maximum(blk[:, 6] - blk[:, 0], 1)
-        starts = np.sort(blk[:, 0])
+        tot = blk[:, END] - blk[:, SETUP]
+        rt = np.maximum(blk[:, END_REAL] - blk[:, START], 1)
+        starts = np.sort(blk[:, START])
         row = {"blocks": int(len(blk)), "MHz": round(float(np.median(tot / rt * 100.0))),
                "block_us": round(float(np.median(rt)) / 100.0, 1),
-               "span_us": round(float(blk[:, 6].max() - starts[0]) / 100.0, 1),
-               "prologue": int(np.median(blk[:, 2] - blk[:, 1])),
-               "loop": int(np.median(blk[:, 3] - blk[:, 2])),
-               "barrier_wait": int(np.median(blk[:, 5])),
-               "epilogue": int(np.median(blk[:, 4] - blk[:, 3])),
-               "epi_wait_barrier": int(np.median(blk[:, 7] - blk[:, 3])),
-               "epi_stage0": int(np.median(blk[:, 8] - blk[:, 7])),
-               "epi_tile0": int(np.median(blk[:, 9] - blk[:, 8])),
-               "epi_stage1": int(np.median(blk[:, 10] - blk[:, 9])),
-               "epi_tile1": int(np.median(blk[:, 11] - blk[:, 10])),
-               "epi_commit": int(np.median(blk[:, 4] - blk[:, 11])),
+               "span_us": round(float(blk[:, END_REAL].max() - starts[0]) / 100.0, 1),
+               "prologue": int(np.median(blk[:, PROLOGUE] - blk[:, SETUP])),
+               "loop": int(np.median(blk[:, LOOP] - blk[:, PROLOGUE])),
+               "barrier_wait": int(np.median(blk[:, BAR_WAIT])),
+               "epilogue": int(np.median(blk[:, END] - blk[:, LOOP])),
+               "epi_wait_barrier": int(np.median(blk[:, EPI_BARRIER] - blk[:, LOOP])),
+               "epi_stage0": int(np.median(blk[:, EPI_TILE] - blk[:, EPI_BARRIER])),
+               "epi_tile0": int(np.median(blk[:, EPI_TILE + 1] - blk[:, EPI_TILE])),
+               "epi_stage1": int(np.median(blk[:, EPI_TILE + 2] - blk[:, EPI_TILE + 1])),
+               "epi_tile1": int(np.median(blk[:, EPI_TILE + 3] - blk[:, EPI_TILE + 2])),
+               "epi_commit": int(np.median(blk[:, END] - blk[:, EPI_TILE + 3])),
                "start_spread_us": [round(float(np.percentile(starts - starts[0], q)) / 100.0, 1)
                                    for q in (25, 50, 75, 100)]}
         out[f"k{kt} {epi}"] = row

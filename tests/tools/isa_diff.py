@@ -15,8 +15,8 @@ sides' register counts, scratch and LDS size from the code-object metadata.
 Exit status 0: every file of both trees identical; 1: any difference (a kernel or file on
 one side only included); 2: a compile failed.  --work keeps the assembly (<work>/a, <work>/b)
 and reuses a file whose source, headers and flags are unchanged.  --define (repeatable) appends
--DNAME=VALUE to both trees' flags, to compare the diagnostic builds (HFG_ABLATE=1,
-HFG_CONV_TIMING=1) as well.
+-DNAME=VALUE to both trees' flags, to compare the diagnostic builds of csrc/diag.h as well,
+one run each: HFG_ABLATE=1, HFG_CONV_TIMING=1, HFG_RB_TIMING=1.
 """
 from __future__ import annotations
 

@@ -5,7 +5,8 @@ GPU box:  python tests/tools/rb_phases.py LIB.so [--precision f16x3]
 Runs 3 V1 [8, 80, 1024] forwards with that library, reads the stamps of the last one and
 prints per kernel instance and launch half: blocks, rounds (distinct start waves), the median
 shader-clock cycles of each phase (prologue, each conv's MFMA loop, each transition, the MRF
-epilogue) and the clock (s_memtime vs the 100 MHz s_memrealtime)."""
+epilogue) and the clock (s_memtime vs the 100 MHz s_memrealtime).  The buffer's shape comes
+from the library (hfg_debug_rb_ts_geometry); the slots are RbTsSlot of csrc/diag.h."""
 import ctypes
 import importlib
 import json
@@ -15,7 +16,10 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-SLOTS, BLOCKS, REGIONS = 24, 8192, 20
+# RbTsSlot (csrc/diag.h): SETUP .. CONV + 2 n_conv are the sequence of clock stamps, TRANS +
+# 2 n_conv the realtime end; from SUB on, the sub-phase stamps
+START, SETUP, PROLOGUE, CONV, TRANS, SUB = 0, 1, 2, 3, 4, 20
+LOADS_ISSUED, X_LANDED, AMAX, MRF_LANDED = 20, 21, 22, 23
 NAMES = {}
 for kt_i, kt in enumerate((3, 7, 11)):
     for wm_i, wm in enumerate(("C32", "C64", "C128")):
@@ -23,6 +27,13 @@ for kt_i, kt in enumerate((3, 7, 11)):
             NAMES[(kt_i * 3 + wm_i) * 2 + half] = f"k{kt} {wm} half{half}"
 NAMES[18] = "k3 C64 narrow half0"
 NAMES[19] = "k3 C64 narrow half1"
+
+
+def geometry(dl, tag):
+    """(slots, blocks, regions) of the library's stamp buffer (csrc/diag.h)."""
+    g = [ctypes.c_int() for _ in range(3)]
+    getattr(dl, f"hfg_debug_{tag}_ts_geometry")(*[ctypes.byref(v) for v in g])
+    return tuple(v.value for v in g)
 
 
 def main():
@@ -55,30 +66,32 @@ def main():
     assert dl.hfg_debug_rb_ts_clear() == 0
     h.forward_ws(mel.data_ptr(), B, T, wav.data_ptr(), out_len, ws.data_ptr(), ws_bytes, st)
     torch.cuda.synchronize(dev)
+    SLOTS, BLOCKS, REGIONS = geometry(dl, "rb")
+    assert SLOTS > MRF_LANDED and REGIONS >= len(NAMES), "stamp layout older than this tool"
     buf = np.zeros(REGIONS * BLOCKS * SLOTS, dtype=np.uint64)
     assert dl.hfg_debug_rb_ts(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
     buf = buf.reshape(REGIONS, BLOCKS, SLOTS).astype(np.int64)
     out = {}
     for r in range(REGIONS):
         blk = buf[r]
-        used = blk[:, 1] != 0
+        used = blk[:, SETUP] != 0
         if not used.any():
             continue
         blk = blk[used]
-        # last filled slot = realtime end (4 + 2 n_conv)
-        nz = (blk[:, :20] != 0).sum(axis=1)
+        # last filled slot = realtime end (TRANS + 2 n_conv)
+        nz = (blk[:, :SUB] != 0).sum(axis=1)
         last = int(np.median(nz)) - 1
-        n_conv = (last - 4) // 2
-        t = blk[:, 1:last].astype(np.float64)  # memtime stamps 1 .. 3 + 2n
+        n_conv = (last - TRANS) // 2
+        t = blk[:, SETUP:last].astype(np.float64)  # clock stamps SETUP .. CONV + 2n
         d = np.diff(t, axis=1)
-        rt = (blk[:, last] - blk[:, 0]).astype(np.float64)  # 100 MHz ticks
+        rt = (blk[:, last] - blk[:, START]).astype(np.float64)  # 100 MHz ticks
         mhz = np.median((t[:, -1] - t[:, 0]) / np.maximum(rt, 1) * 100.0)
         names = ["prologue"]
         for cv in range(n_conv):
             names += [f"conv{cv}", f"trans{cv}"]
         names += ["epilogue"]
         med = np.median(d, axis=1 - 1)
-        starts = np.sort(blk[:, 0])
+        starts = np.sort(blk[:, START])
         # rounds: gaps in the start times larger than half a block time
         blk_ticks = np.median(rt)
         rounds = 1 + int((np.diff(starts) > 0.5 * blk_ticks).sum())
@@ -89,12 +102,14 @@ def main():
                "cycles": {n: int(v) for n, v in zip(names, med)},
                "frac": {n: round(float(v) / tot, 3) for n, v in zip(names, med)}}
         sub = {}
-        if (blk[:, 22] != 0).all():
-            sub = {"setup": blk[:, 20] - blk[:, 1], "x_wait": blk[:, 21] - blk[:, 20],
-                   "amax_bar": blk[:, 22] - blk[:, 21], "op_write": blk[:, 2] - blk[:, 22]}
-        if (blk[:, 23] != 0).all():
-            sub["mrf_wait"] = blk[:, 23] - blk[:, 2 + 2 * n_conv]
-            sub["mrf_store"] = blk[:, 3 + 2 * n_conv] - blk[:, 23]
+        if (blk[:, AMAX] != 0).all():
+            sub = {"setup": blk[:, LOADS_ISSUED] - blk[:, SETUP],
+                   "x_wait": blk[:, X_LANDED] - blk[:, LOADS_ISSUED],
+                   "amax_bar": blk[:, AMAX] - blk[:, X_LANDED],
+                   "op_write": blk[:, PROLOGUE] - blk[:, AMAX]}
+        if (blk[:, MRF_LANDED] != 0).all():
+            sub["mrf_wait"] = blk[:, MRF_LANDED] - blk[:, CONV - 1 + 2 * n_conv]
+            sub["mrf_store"] = blk[:, CONV + 2 * n_conv] - blk[:, MRF_LANDED]
         row["sub"] = {k: int(np.median(v)) for k, v in sub.items()}
         out[NAMES.get(r, str(r))] = row
         print(NAMES.get(r, str(r)), json.dumps(row))

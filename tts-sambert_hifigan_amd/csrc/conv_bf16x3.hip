@@ -44,18 +44,10 @@
 #define HFG_AREG_NVST 6
 #endif
 
-// diagnostic build only (-DHFG_CONV_TIMING=1, profiles/r04): wave 0 of every tile-5 block
-// stamps the shader clock (start, prologue end, loop end, epilogue end) and sums its
-// barrier waits into g_cv_ts (one region per KT), read back by hfg_debug_cv_ts
-#ifndef HFG_CONV_TIMING
-#define HFG_CONV_TIMING 0
-#endif
-
 namespace hfg {
 
 #if HFG_CONV_TIMING
-constexpr int kCvTsSlots = 16, kCvTsBlocks = 8192, kCvTsRegions = 12;
-__device__ uint64_t g_cv_ts[kCvTsRegions * kCvTsBlocks * kCvTsSlots];
+__device__ uint64_t g_cv_ts[kCvTs.words()];  // the clock stamps of this kernel (diag.h)
 #endif
 
 template <int KT_, int TPC, int WAVES_M, int WAVES_N, int WM, int WN, int WD, bool UPS, int NP,
@@ -210,7 +202,7 @@ conv1d_bf16x3(const ConvParams p) {
       const int i = tid + q * NT;
       const int t = i >> 1;
       // (ablation bit7: always re-read channel group 0, i.e. L2-warm loads)
-      const int cb = ((kAblate && (p.dbg & 128)) ? 0 : g) * 16 + (i & 1) * 8;
+      const int cb = ((kAblate && (p.dbg & kAblConvWarmX)) ? 0 : g) * 16 + (i & 1) * 8;
       const int gi = wbase + t;
       const bool tok = (i < 2 * XW) && ((unsigned)gi < (unsigned)L_in_b);
       // byte offsets from the block-uniform base: SGPR base + 32-bit VGPR offset loads
@@ -251,7 +243,7 @@ conv1d_bf16x3(const ConvParams p) {
       const int i = tid + q * NT;
       if (AREG || i < 2 * XW) {
         bf16x8 h, l;
-        if (kAblate && UPS && (p.dbg & 256)) {
+        if (kAblate && UPS && (p.dbg & kAblConvUpsRawX)) {
           // ablation (upsamplers, timing only): the raw fp32 halves, no pre-activation or split
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
@@ -378,19 +370,19 @@ conv1d_bf16x3(const ConvParams p) {
 
 #if HFG_CONV_TIMING
   uint64_t* const cts = g_cv_ts + ((size_t)((KT_ == 3 ? 0 : KT_ == 7 ? 1 : KT_ == 11 ? 2 : 3) * 3 +
-                                           (p.res ? ((p.mrf && (p.mrf_mode & 1)) ? 2 : 1) : 0)) * kCvTsBlocks +
-                                   ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) % kCvTsBlocks) *
-                                      kCvTsSlots;
+                                           (p.res ? ((p.mrf && (p.mrf_mode & 1)) ? 2 : 1) : 0)) * kCvTs.blocks +
+                                   ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) % kCvTs.blocks) *
+                                      kCvTs.slots;
   // stamps kept in SGPRs and stored once at the end: a stamp store mid-kernel would make
   // every later vmcnt wait also wait for its write (one in-order queue for loads and stores)
-  uint64_t tsv[16] = {};
+  uint64_t tsv[kCvTs.slots] = {};
   auto cstamp = [&](int i) { tsv[i] = __builtin_amdgcn_s_memtime(); };
   uint64_t bar_wait = 0;
-  tsv[0] = __builtin_amdgcn_s_memrealtime();
+  tsv[kCvTsStart] = __builtin_amdgcn_s_memrealtime();
   // placement: HW_ID (CU, SE, SIMD, wave) and XCC of wave 0
-  tsv[12] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+  tsv[kCvTsHwId] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
             ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-  cstamp(1);
+  cstamp(kCvTsSetup);
   uint64_t* const epi_ts = tsv;  // the epilogue's stamps (conv_epilogue_lds2)
 #else
   auto cstamp = [](int) {};
@@ -413,7 +405,7 @@ conv1d_bf16x3(const ConvParams p) {
   store_x(Xbuf0);
   wait_vm<0>();
   lds_barrier();
-  cstamp(2);
+  cstamp(kCvTsPrologue);
 
   if constexpr (AREG) {
     // ---- A fragments from global into registers, AD taps ahead; one barrier per
@@ -466,7 +458,7 @@ conv1d_bf16x3(const ConvParams p) {
                       (tap + k / WN) * p.dil * 8;
       bh[k & 1] = *reinterpret_cast<const bf16x8*>(Xh + off);
       // ablation bit 12: no lo-plane reads (the hi fragment stands in; half the LDS reads)
-      bl[k & 1] = (kAblate && (p.dbg & 4096)) ? bh[k & 1]
+      bl[k & 1] = (kAblate && (p.dbg & kAblConvNoLoB)) ? bh[k & 1]
                                               : *reinterpret_cast<const bf16x8*>(Xh + xplane + off);
     };
     static_assert(WN % 2 == 0, "B ring parity across taps");
@@ -541,16 +533,16 @@ conv1d_bf16x3(const ConvParams p) {
 #if HFG_CONV_TIMING
       const uint64_t tb0 = __builtin_amdgcn_s_memtime();
 #endif
-      if (!(kAblate && (p.dbg & 4))) lds_barrier();
+      if (!(kAblate && (p.dbg & kAblConvNoBarrier))) lds_barrier();
 #if HFG_CONV_TIMING
       bar_wait += __builtin_amdgcn_s_memtime() - tb0;
 #endif
     }
 #if HFG_CONV_TIMING
-    tsv[5] = bar_wait;
+    tsv[kCvTsBarWait] = bar_wait;
 #endif
     prio_other();
-    cstamp(3);
+    cstamp(kCvTsLoop);
   } else if constexpr (KT_ > 0 && WM * WN >= 8) {
     // ---- 64x128-per-wave tile, compile-time taps: the chunk loop unrolled over one
     // channel group, so the chunks that stage the next input window are their own
@@ -615,7 +607,7 @@ conv1d_bf16x3(const ConvParams p) {
         // the slab of chunk c+1 must have landed; younger: this chunk's input loads
         if (ISX && !STX) wait_x(std::integral_constant<int, NX>{});
         else wait_vm<0>();
-        if (!(kAblate && (p.dbg & 4))) lds_barrier();
+        if (!(kAblate && (p.dbg & kAblConvNoBarrier))) lds_barrier();
         wslot ^= 1;
       }
     }
@@ -631,8 +623,8 @@ conv1d_bf16x3(const ConvParams p) {
     const __bf16* Ws = Wbuf0 + wslot * SLAB;
     const __bf16* Xh = Xbuf0 + (g & 1) * xbuf;
     const bool more_groups = (g + 1) * n_tg < p.n_chunks;
-    const bool issue_x = more_groups && tg == xg && !(kAblate && (p.dbg & 1));
-    const bool store_now = more_groups && tg == n_tg - 1 && !(kAblate && (p.dbg & 1));
+    const bool issue_x = more_groups && tg == xg && !(kAblate && (p.dbg & kAblConvNoRestage));
+    const bool store_now = more_groups && tg == n_tg - 1 && !(kAblate && (p.dbg & kAblConvNoRestage));
     // always PW pieces per thread, so every vmcnt below is a constant: past the last
     // chunk the last slab is re-read into the free slot (that of chunk c-1).  (The slot
     // steps and wraps at 2 here; toggling it, wslot ^ 1 as in the unrolled loop above,
@@ -673,11 +665,11 @@ conv1d_bf16x3(const ConvParams p) {
     // when a later chunk consumes them.
     if (issue_x && !store_now) wait_x(std::integral_constant<int, NX>{});
     else wait_vm<0>();
-    if (!(kAblate && (p.dbg & 4))) lds_barrier();
+    if (!(kAblate && (p.dbg & kAblConvNoBarrier))) lds_barrier();
     if (++wslot == 2) wslot = 0;
   }
   }
-  if (kAblate && (p.dbg & 8)) {  // ablation: no epilogue
+  if (kAblate && (p.dbg & kAblConvNoEpilogue)) {  // ablation: no epilogue
     if (acc[0][0][0] == 1.2345e-30f) p.y[0] = acc[WM - 1][WN - 1][15];
     return;
   }
@@ -783,7 +775,7 @@ conv1d_bf16x3(const ConvParams p) {
       // LDS-DMA is still in flight (it counts in vmcnt, not lgkmcnt)
       wait_vm<0>();
       lds_barrier();
-      cstamp(7);
+      cstamp(kCvTsEpiBarrier);
       float* stage = reinterpret_cast<float*>(lds16) + wave * epi_stage_wave(WN);
       if constexpr (AREG)
         conv_epilogue_lds2<WM, WN>(p, acc, b, mt * MT + wave_m * 32 * WM, mt * MT,
@@ -797,12 +789,12 @@ conv1d_bf16x3(const ConvParams p) {
                             half, col, sc);
     }
   }
-  cstamp(4);
+  cstamp(kCvTsEnd);
 #if HFG_CONV_TIMING
-  tsv[6] = __builtin_amdgcn_s_memrealtime();
+  tsv[kCvTsEndReal] = __builtin_amdgcn_s_memrealtime();
   if (AREG && tid == 0)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) cts[i] = tsv[i];
+    for (int i = 0; i < kCvTs.slots; ++i) cts[i] = tsv[i];
 #endif
 }
 
@@ -884,13 +876,5 @@ hipError_t launch_conv_bf16x3(int tile, int kt, bool ups, int fmt, int np, const
 }  // namespace hfg
 
 #if HFG_CONV_TIMING
-extern "C" int hfg_debug_cv_ts(void* dst, size_t bytes) {
-  if (bytes > sizeof(hfg::g_cv_ts)) bytes = sizeof(hfg::g_cv_ts);
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(hfg::g_cv_ts), bytes, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int hfg_debug_cv_ts_clear() {
-  static uint64_t* z = nullptr;
-  if (!z) z = (uint64_t*)calloc(1, sizeof(hfg::g_cv_ts));
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(hfg::g_cv_ts), z, sizeof(hfg::g_cv_ts), 0, hipMemcpyHostToDevice);
-}
+HFG_TS_ENTRIES(cv, hfg::g_cv_ts, hfg::kCvTs)
 #endif

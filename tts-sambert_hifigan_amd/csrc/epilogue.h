@@ -319,8 +319,8 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
                                                    int N_b, int half, int col, float* stage,
                                                    const float* bias_lds, int lane, float sc,
                                                    uint64_t* tsv = nullptr) {
-  // tsv (clock-stamp diagnostic builds): row tile i's staging done -> tsv[8 + 2i], its stores
-  // issued -> tsv[9 + 2i] (registers: the caller stores them at the end)
+  // tsv (clock-stamp diagnostic builds): row tile i's staging done -> tsv[kCvTsEpiTile + 2i], its
+  // stores issued -> the slot after it (registers: the caller stores them at the end)
   auto ts = [&](int s_) {
     if (tsv) tsv[s_] = __builtin_amdgcn_s_memtime();
   };
@@ -343,7 +343,7 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
         stage[(acc_row(r, half)) * SROW + k * 32 + col] = acc[i][k][r];
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's writes are in LDS
     __builtin_amdgcn_wave_barrier();
-    ts(8 + 2 * i);
+    ts(kCvTsEpiTile + 2 * i);
     // wave-uniform: the whole 32 x 32*WN tile of this row tile lies inside [0, M) x [0, N_b)
     // -> unmasked float4 stores (the masked path branches per element)
     const bool interior = __builtin_amdgcn_readfirstlane(row_base) + i * 32 + 31 < p.M &&
@@ -362,11 +362,11 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
         const int row = row_base + i * 32 + rr, n = n_base + 4 * c4;
         const bool ok = row < p.M && n < N_b;
         const int64_t o = (int64_t)row * p.N + n;
-        // ablation bits 15 / 16 (timing only): the residual read from the tile's columns of row
-        // 0 (L2-warm after the first wave) / not read at all
-        const int64_t orr = (kAblate && (p.dbg & 32768)) ? (int64_t)n : o;
+        // ablations (timing only): the residual read from the tile's columns of row 0 (L2-warm
+        // after the first wave) / not read at all
+        const int64_t orr = (kAblate && (p.dbg & kAblEpiWarmRes)) ? (int64_t)n : o;
         if constexpr (R)
-          rv[j] = ok && !(kAblate && (p.dbg & 65536)) ? *reinterpret_cast<const float4*>(resb + orr)
+          rv[j] = ok && !(kAblate && (p.dbg & kAblEpiNoRes)) ? *reinterpret_cast<const float4*>(resb + orr)
                                                       : float4{0.f, 0.f, 0.f, 0.f};
         if constexpr (M)
           mv[j] = ok ? *reinterpret_cast<const float4*>(outb + o) : float4{0.f, 0.f, 0.f, 0.f};
@@ -416,8 +416,8 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
         typedef float f4v __attribute__((ext_vector_type(4)));
         if (interior) {
           vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-          if (kAblate && (p.dbg & 16384)) {
-            // ablation bit 14: no stores (timing only)
+          if (kAblate && (p.dbg & kAblEpiNoStore)) {
+            // ablation: no stores (timing only)
             if (v.x == 1.2345e-30f) dst[0] = v.y;
           } else {
             // streamed once (the next launch reads it from HBM / MALL): non-temporal
@@ -459,7 +459,7 @@ __device__ __forceinline__ void conv_epilogue_lds2(const ConvParams& p, floatx16
     } else {
       batch(IFull{}, F_{}, F_{}, Z{});
     }
-    ts(9 + 2 * i);
+    ts(kCvTsEpiTile + 2 * i + 1);
     __builtin_amdgcn_wave_barrier();
   });
   if (p.amax_out) amax_commit(vmax, p.amax_out, b);

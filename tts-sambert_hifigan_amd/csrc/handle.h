@@ -4,7 +4,8 @@
 //   plan.cpp     config validation, the plan, shapes and workspace sizing (no HIP runtime call)
 //   pack.cpp     weights -> the kernels' packed operand orders (host)
 //   forward.cpp  the launch schedule, the weight upload
-//   hifigan_capi.cpp  the C ABI (include/hifigan_hip.h, hifigan_hip_inspect.h)
+//   hifigan_capi.cpp  the C ABI of include/hifigan_hip.h, the parameter store
+//   inspect_capi.cpp  the C ABI of include/hifigan_hip_inspect.h, the schedule-knob store
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,6 +25,8 @@ namespace hfg_host {
 // the calling thread's hfg_last_error text; returns code
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_fail(hipError_t e, const char* what);
+// How a text-returning entry ends: s and its NUL into buf, or HFG_EINVAL naming the size needed
+int return_text(const std::string& s, char* buf, size_t buflen);
 
 // Schedule overrides for A/B runs and the parity suites (hfg_debug_schedule_set): a
 // process-wide table read when a handle is created.  The library reads no environment
@@ -262,6 +265,10 @@ int n_slots(const hfg_handle* h);
 // ---- pack.cpp ---------------------------------------------------------------
 // Every weight set -> h->packed_host (HFG_EAGAIN while one is missing); sets Layer::ew.
 int pack_weights(hfg_handle* h);
+
+// ---- hifigan_capi.cpp ---------------------------------------------------------
+// what every generator forward entry refuses: NULL, host-only and MRF-only handles
+int check_generator(const hfg_handle* h);
 
 // ---- forward.cpp ------------------------------------------------------------
 // pack_weights, then (device handles) the upload; clears h->dirty

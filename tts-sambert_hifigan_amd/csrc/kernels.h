@@ -8,6 +8,8 @@
 #include <mutex>
 #include <stdint.h>
 
+#include "diag.h"
+
 namespace hfg {
 
 // One-time launch setup of a kernel entry, safe across threads and devices:
@@ -70,17 +72,8 @@ struct ConvParams {
   const uint32_t* amax_in;
   uint32_t* amax_out;
   int ew;
-  int dbg;           // ablation flags (HFG_DEBUG_FLAGS, builds with -DHFG_ABLATE=1 only; wrong
-                     // results when set), bf16x3 kernel: bit0 skip input restaging after the
-                     // first chunk, bit2 no per-chunk barrier, bit3 no epilogue, bit7 every
-                     // group's input loads re-read group 0 (L2-warm)
+  int dbg;           // ablation bits (diag.h)
 };
-
-// kernel ablation switches (timing experiments) exist only in -DHFG_ABLATE=1 builds
-#ifndef HFG_ABLATE
-#define HFG_ABLATE 0
-#endif
-constexpr bool kAblate = HFG_ABLATE != 0;
 
 // Tile configurations of conv1d_mfma_f32 (fp32 MFMA 32x32x2).
 //   MT = 32*WM*WAVES_M rows, NTILE = 32*WN*WAVES_N columns,
@@ -218,8 +211,7 @@ struct UpsParams {
   const uint32_t* amax_in;  // f16x3: per-item max |x| (producer slot) or null
   uint32_t* amax_out;       // f16x3: per-item max |y| slot or null
   int ew;                   // weight packing exponent (f16x3)
-  int dbg;               // ablations (HFG_DEBUG_FLAGS, timing only, wrong results): bit9 no
-                         // input conversion after group 0, bit10 no input loads after group 0
+  int dbg;               // ablation bits (diag.h)
 };
 size_t ups_lds_bytes(int cfg);
 hipError_t launch_ups_bf16x3(int cfg, int fmt, int np, const UpsParams& p, hipStream_t stream,
@@ -266,8 +258,7 @@ struct RbParams {
   // per block, else the launch runs min(windows, persist) blocks that walk the windows and
   // overlap each window's MRF read-modify-write with the next window's x loads
   int persist;
-  int dbg;               // ablations (HFG_DEBUG_FLAGS, wrong results when set): bit4 no MRF
-                         // epilogue, bit5 no x loads, bit6 no operand writes
+  int dbg;               // ablation bits (diag.h)
   float post_slope;      // fused conv_post: slope of the leaky_relu in front of it
 };
 // divisors whose fma-refined reciprocal quotient equals the IEEE quotient for every fp32

@@ -92,7 +92,8 @@ constexpr UpsLds ups_lds(const UpsCfg& t) {
 
 // ---- resblock_bf16x3 / resblock2_bf16x3 (resblock_body.h) ----
 // [C/16 groups x 2 half-groups x (hi, lo) planes of [row][8 bf16]][n_conv * C biases]
-// [16 per-wave maxima (f16x3)]; the fused conv_post stages its rows over the planes
+// [16 per-wave maxima (f16x3)][diagnostic build: the clock stamps]; the fused conv_post stages
+// its rows over the planes
 struct RbLds {
   int rows;      // operand rows: the window plus rb_marg spare rows a side
   int ps;        // bytes per plane
@@ -100,10 +101,12 @@ struct RbLds {
   int gs;        // 16-channel group
   int bias_off;  // bytes: past the operand planes
   int bias_conv; // floats: one conv's biases; the per-wave maxima follow n_conv of them
+  int amax_n;    // floats: the per-wave maxima; the clock stamps follow them
+  int ts_bytes;  // the clock stamps of a -DHFG_RB_TIMING=1 build (diag.h), else 0
   int post_row;  // fused conv_post: row stride of its staging (floats): the two lane halves'
                  // rows, 4 apart, land 32 banks apart
   constexpr size_t total(int n_conv) const {
-    return (size_t)bias_off + sizeof(float) * ((size_t)n_conv * bias_conv + 16);
+    return (size_t)bias_off + sizeof(float) * ((size_t)n_conv * bias_conv + amax_n) + ts_bytes;
   }
 };
 constexpr RbLds rb_lds(int C, int nwin) {
@@ -114,6 +117,8 @@ constexpr RbLds rb_lds(int C, int nwin) {
   l.gs = 2 * l.hps;
   l.bias_off = C / 16 * l.gs;
   l.bias_conv = C;
+  l.amax_n = 16;
+  l.ts_bytes = HFG_RB_TIMING ? kRbTs.slots * (int)sizeof(uint64_t) : 0;
   l.post_row = nwin + 8;
   return l;
 }

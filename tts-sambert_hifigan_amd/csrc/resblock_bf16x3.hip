@@ -43,18 +43,10 @@
 #include "kernels.h"
 #include "launch.h"
 
-// diagnostic build only (-DHFG_RB_TIMING=1, profiles/r04): wave 0 of every block stamps the
-// shader clock at the phase boundaries into g_rb_ts (one region per instance and launch half),
-// read back by hfg_debug_rb_ts (tests/tools/rb_phases.py)
-#ifndef HFG_RB_TIMING
-#define HFG_RB_TIMING 0
-#endif
-
 namespace hfg {
 
 #if HFG_RB_TIMING
-constexpr int kRbTsSlots = 24, kRbTsBlocks = 8192, kRbTsRegions = 20;
-__device__ uint64_t g_rb_ts[kRbTsRegions * kRbTsBlocks * kRbTsSlots];
+__device__ uint64_t g_rb_ts[kRbTs.words()];  // the clock stamps of these kernels (diag.h)
 #endif
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -205,10 +197,7 @@ hipError_t launch_rb(EntryRb* e, const char* kernel, int C, int nwin, int kt, co
   if (p.W <= 0 || p.halo < 0 || p.W + 2 * p.halo > nwin) return hipErrorInvalidValue;
   for (int i = 0; i < p.n_conv; ++i)
     if (p.dil[i] < 1 || (kt - 1) / 2 * p.dil[i] > rb_marg(C, nwin)) return hipErrorInvalidValue;
-  size_t lds = rb_lds_bytes(C, nwin, p.n_conv);
-#if HFG_RB_TIMING
-  lds += kRbTsSlots * 8;  // + the stamps
-#endif
+  const size_t lds = rb_lds_bytes(C, nwin, p.n_conv);
   const int n_tiles = (p.L + p.W - 1) / p.W;
   dim3 grid(n_tiles, batch);
   if (p.persist) {
@@ -265,13 +254,5 @@ hipError_t launch_resblock2_bf16x3(int C, int nwin, int wm, int kt, int fmt, int
 }  // namespace hfg
 
 #if HFG_RB_TIMING
-extern "C" int hfg_debug_rb_ts(void* dst, size_t bytes) {
-  if (bytes > sizeof(hfg::g_rb_ts)) bytes = sizeof(hfg::g_rb_ts);
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(hfg::g_rb_ts), bytes, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int hfg_debug_rb_ts_clear() {
-  static uint64_t* z = nullptr;
-  if (!z) z = (uint64_t*)calloc(1, sizeof(hfg::g_rb_ts));
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(hfg::g_rb_ts), z, sizeof(hfg::g_rb_ts), 0, hipMemcpyHostToDevice);
-}
+HFG_TS_ENTRIES(rb, hfg::g_rb_ts, hfg::kRbTs)
 #endif

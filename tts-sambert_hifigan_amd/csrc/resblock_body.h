@@ -88,19 +88,19 @@ resblock_bf16x3(const RbParams p) {
                         : ((KT == 3 ? 0 : KT == 7 ? 1 : 2) * 3 + (C == 32 ? 0 : C == 64 ? 1 : 2)) * 2 +
                               (p.conv0 > 0 ? 1 : 0);
   const int ts_blk = blockIdx.y * gridDim.x + blockIdx.x;
-  uint64_t* const ts = g_rb_ts + ((size_t)ts_region * kRbTsBlocks + (ts_blk < kRbTsBlocks ? ts_blk : 0)) * kRbTsSlots;
+  uint64_t* const ts = g_rb_ts + ((size_t)ts_region * kRbTs.blocks + (ts_blk < kRbTs.blocks ? ts_blk : 0)) * kRbTs.slots;
   // stamps kept in LDS (past the f16x3 maxima) and stored once at the end: a global (or
   // scratch) store mid-kernel would make every later vmcnt wait also wait for its write (one
   // in-order queue for vector loads and stores).  A persistent block keeps its last window's.
-  uint64_t* const tsv = reinterpret_cast<uint64_t*>(amax_s + 16);
+  uint64_t* const tsv = reinterpret_cast<uint64_t*>(amax_s + LY.amax_n);
   auto stamp = [&](int i) {
     const uint64_t t = __builtin_amdgcn_s_memtime();
     if (tid == 0) tsv[i] = t;
   };
-  if (tid < kRbTsSlots) tsv[tid] = 0;
+  if (tid < kRbTs.slots) tsv[tid] = 0;
   __syncthreads();
-  if (tid == 0) tsv[0] = __builtin_amdgcn_s_memrealtime();
-  stamp(1);
+  if (tid == 0) tsv[kRbTsStart] = __builtin_amdgcn_s_memrealtime();
+  stamp(kRbTsSetup);
 #else
   auto stamp = [](int) {};
 #endif
@@ -142,7 +142,7 @@ resblock_bf16x3(const RbParams p) {
   };
   load_a(0, Q0);
   load_a(1, Q0 + 1);
-  stamp(20);
+  stamp(kRbTsLoadsIssued);
 
   // ---- x and the MRF accumulator of utterance b through buffer descriptors ----
   // Element (row, column) sits at soffset = (row0 + row part of accumulator element r) * L * 4
@@ -173,9 +173,9 @@ resblock_bf16x3(const RbParams p) {
     }
   };
   auto mask_x = [&]() {
-    // ablation bit 5 zeroes x after the loads (a select on a uniform flag inside the load
+    // the ablation zeroes x after the loads (a select on a uniform flag inside the load
     // expression made the compiler branch per element)
-    const bool xz = kAblate && (dbg & 32);
+    const bool xz = kAblate && (dbg & kAblRbZeroX);
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -323,7 +323,7 @@ resblock_bf16x3(const RbParams p) {
   // VALU costs ~22 cycles more per instruction than its two scalar halves beside MFMAs
   // (MI355X_MICROARCH.md; same-box -0.9 % ResBlock time, profiles/r06/ab_rewrite.txt).
   auto write_operand = [&](const floatx16 (&v)[WM][WN], float sc) {
-    if (kAblate && (dbg & 64)) return;
+    if (kAblate && (dbg & kAblRbNoOperand)) return;
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
       const float f1 = vk[k] ? sc : 0.0f, f2 = vk[k] ? kLReluSlope * sc : 0.0f;
@@ -404,8 +404,8 @@ resblock_bf16x3(const RbParams p) {
 #pragma unroll
       for (int k = 0; k < WN; ++k) {
         bh[buf][k] = *reinterpret_cast<const bf16x8*>(src + k * 512);
-        // ablation bit 11: no lo-plane reads (the hi fragment stands in; half the LDS reads)
-        bl[buf][k] = (kAblate && (dbg & 2048)) ? bh[buf][k]
+        // ablation: no lo-plane reads (the hi fragment stands in; half the LDS reads)
+        bl[buf][k] = (kAblate && (dbg & kAblRbNoLoB)) ? bh[buf][k]
                                                : *reinterpret_cast<const bf16x8*>(src + k * 512 + PS);
       }
     };
@@ -470,7 +470,7 @@ resblock_bf16x3(const RbParams p) {
     if constexpr (FMT == kFmtF16) {
 #if HFG_RB_TIMING
       wait_vm<0>();
-      stamp(21);
+      stamp(kRbTsXLanded);
 #endif
       float mm = 0.f;  // the margin columns are part of the first operand
 #pragma unroll
@@ -480,14 +480,14 @@ resblock_bf16x3(const RbParams p) {
       wave_amax(xcur, 0, mm);
       lds_barrier();
       ex = block_exp();
-      stamp(22);
+      stamp(kRbTsAmax);
     } else if (PERSIST) {
       lds_barrier();  // every wave has read x from LDS (the copy the operand overwrites)
     }
     write_operand(xcur, exp2i(ex));
     write_margins(exp2i(ex));
     lds_barrier();
-    stamp(2);
+    stamp(kRbTsPrologue);
 
     if constexpr (RB2) {
       // ResBlock2: x = x + (conv_m(lrelu(x)) + b_m); x is rewritten as the next conv's operand
@@ -540,7 +540,7 @@ resblock_bf16x3(const RbParams p) {
     } else {
       for (int cv = 0; cv < n_conv; cv += 2) {
         run_conv(cv);
-        stamp(3 + 2 * cv);
+        stamp(kRbTsConv + 2 * cv);
         finalize(cv);
         if (cv > 0) radius += (KT - 1) / 2 * p.dil[cv];  // conv 0: exact (margins from x)
         wave_amax(acc, radius);
@@ -548,9 +548,9 @@ resblock_bf16x3(const RbParams p) {
         ex = block_exp();
         write_operand(acc, exp2i(ex));
         lds_barrier();
-        stamp(4 + 2 * cv);
+        stamp(kRbTsTrans + 2 * cv);
         run_conv(cv + 1);
-        stamp(5 + 2 * cv);
+        stamp(kRbTsConv + 2 * (cv + 1));
         finalize(cv + 1);
         radius += (KT - 1) / 2;  // conv2: dilation 1
 #pragma unroll
@@ -566,7 +566,7 @@ resblock_bf16x3(const RbParams p) {
           write_operand(xcur, exp2i(ex));
           lds_barrier();
         }
-        stamp(6 + 2 * cv);
+        stamp(kRbTsTrans + 2 * (cv + 1));
       }
     }
 
@@ -587,7 +587,7 @@ resblock_bf16x3(const RbParams p) {
       ok[k] = vk[k] && c >= c_lo && c < c_hi;
       vo[k] = ok[k] ? (lrow + (unsigned)(ws + c)) * 4u : 0u;
     }
-    const bool skip_mrf = kAblate && (dbg & 16);  // ablation: no MRF epilogue
+    const bool skip_mrf = kAblate && (dbg & kAblRbNoMrf);  // ablation: no MRF epilogue
     // persistent grid: the next window's x copy is issued first, then the MRF loads, so the
     // two round trips overlap (one wait for both)
     int bn = b, len_n = len_b, wsn = ws;
@@ -618,7 +618,7 @@ resblock_bf16x3(const RbParams p) {
     if (add && !skip_mrf) {
 #if HFG_RB_TIMING
       wait_vm<0>();
-      stamp(23);
+      stamp(kRbTsMrfLanded);
 #endif
 #pragma unroll
       for (int i = 0; i < WM; ++i)
@@ -666,7 +666,7 @@ resblock_bf16x3(const RbParams p) {
             }
         }
       }
-      stamp(3 + 2 * n_conv);
+      stamp(kRbTsConv + 2 * n_conv);
       if (p.amax_out) {  // f16x3 consumers of the stage output (block-uniform branch)
         float m = 0.f;
 #pragma unroll
@@ -697,8 +697,8 @@ resblock_bf16x3(const RbParams p) {
   }
 #if HFG_RB_TIMING
   if (tid == 0) {
-    tsv[4 + 2 * n_conv] = __builtin_amdgcn_s_memrealtime();
-    for (int i = 0; i < kRbTsSlots; ++i) ts[i] = tsv[i];
+    tsv[kRbTsTrans + 2 * n_conv] = __builtin_amdgcn_s_memrealtime();
+    for (int i = 0; i < kRbTs.slots; ++i) ts[i] = tsv[i];
   }
 #endif
 }
