@@ -9,9 +9,8 @@
 //
 // GEMM mapping: M = output channels, N = time, K = (tap, channel).  One MFMA
 // k-step covers 16 input channels of ONE tap (lane half h holds channels 8h..8h+7).
-//   * A (weights): split and packed on the host in fragment order
-//     [m_tile][ch_group][tap_group][tap][plane hi/lo][wave_m][wm][lane][8],
-//     so a chunk's slab is one contiguous run copied to LDS by
+//   * A (weights): split and packed on the host in fragment order (conv_bf16x3_pack,
+//     pack_layout.h), so a chunk's slab is one contiguous run copied to LDS by
 //     global_load_lds_dwordx4 (no VGPRs, no conversion on the device).
 //   * B (activations): staged transposed as [t][16 ch] bf16 planes (hi, lo),
 //     row stride 48 B (conflict-free ds_read_b128); pre-activation leaky_relu
@@ -69,8 +68,10 @@ conv1d_bf16x3(const ConvParams p) {
   constexpr ConvBf16x3Lds LY = conv_bf16x3_lds(TCFG, KT_MAX, 0);
   static_assert(conv_bf16x3_lds(TCFG, KT_MAX, LY.xw_max).total(!UPS) <= (int)kMaxLdsBytes, "LDS");
   constexpr int XROW = kBf16x3XRow;  // bf16 per staged row, 16-B halves XOR-swizzled
+  constexpr ConvBf16x3Pack PK = conv_bf16x3_pack(TCFG);  // the A strides (pack_layout.h)
   constexpr int SLAB = LY.slab;                   // bf16 per chunk slab
-  constexpr int TAP_ELEMS = SLAB / TPC;           // bf16 per tap of a slab (hi+lo)
+  static_assert(SLAB == PK.slab, "the LDS slab is the global slab");
+  constexpr int TAP_ELEMS = PK.tap;               // bf16 per tap of a slab (hi+lo)
   constexpr int XW_MAX = LY.xw_max;
   constexpr int XQ = LY.xq;                       // staging tasks per thread
   static_assert(XQ * 8 <= 32, "ok mask");
@@ -303,9 +304,9 @@ conv1d_bf16x3(const ConvParams p) {
     const __bf16* Xl = Xh + xplane;
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * 512 + lane * 8;
+      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * PK.row_tile + lane * PK.lane;
       f.ah[i] = *reinterpret_cast<const bf16x8*>(a);
-      f.al[i] = *reinterpret_cast<const bf16x8*>(a + WAVES_M * WM * 512);
+      f.al[i] = *reinterpret_cast<const bf16x8*>(a + PK.plane);
     }
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
@@ -331,9 +332,9 @@ conv1d_bf16x3(const ConvParams p) {
     bf16x8 ah[WM], al[WM], bh[2], bl[2];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * 512 + lane * 8;
+      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * PK.row_tile + lane * PK.lane;
       ah[i] = *reinterpret_cast<const bf16x8*>(a);
-      al[i] = *reinterpret_cast<const bf16x8*>(a + WAVES_M * WM * 512);
+      al[i] = *reinterpret_cast<const bf16x8*>(a + PK.plane);
     }
     auto ldb = [&](int k) {
       const int t = wave_n * 32 * WN + k * 32 + col + tap * p.dil;
@@ -434,19 +435,19 @@ conv1d_bf16x3(const ConvParams p) {
     // lane's 16 B (no 64-bit address VGPRs per tap)
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)wsrc, 0, (int)((int64_t)p.n_chunks * SLAB * 2), 0x00020000);
-    const int a_lane = lane * 16;
+    const int a_lane = lane * (2 * PK.lane);
     typedef bf16x8 ASet[2][WM];
     ASet a0, a1, a2;
     (void)a2;
     auto load_a = [&](ASet& d, int g, int t) {
-      const int so = ((g * NTG + t / TPC) * SLAB + (t % TPC) * TAP_ELEMS + wm_u * WM * 512) * 2;
+      const int so = ((g * NTG + t / TPC) * SLAB + (t % TPC) * TAP_ELEMS + wm_u * WM * PK.row_tile) * 2;
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
         for (int i = 0; i < WM; ++i)
           d[pl][i] = __builtin_bit_cast(
               bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                          wrs, a_lane + (pl * WAVES_M * WM + i) * 1024, so, 0));
+                          wrs, a_lane + (pl * WAVES_M * WM + i) * (2 * PK.row_tile), so, 0));
     };
     // B fragments: a two-deep ring over the column tiles that carries across the taps of
     // a channel group (the last tile of tap t reads tap t+1's first pair), so a tap's first

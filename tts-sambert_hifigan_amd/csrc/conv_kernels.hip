@@ -61,7 +61,12 @@ conv1d_mfma_f32(const ConvParams p) {
   const int XW = NTILE + (KT - 1) * p.dil;
   const int nx = conv_f32_nx(CK, XW);         // (the LDS terms: lds_layout.h)
   const float inv_xw = 1.0f / (float)XW;
-  const int wchunk = conv_f32_wchunk(MT, CK, KT);  // floats per weight slab
+  // the A strides: pack_layout.h
+  const int wchunk = conv_f32_slab(MT, CK, KT);  // floats per weight slab
+  constexpr ConvF32Pack PK = conv_f32_pack(TileCfg{WM, WN, WAVES_M, WAVES_N}, CK);
+  static_assert(PK.lane == WM && PK.wave_m == 64 * WM && PK.kk == WAVES_M * PK.wave_m &&
+                    PK.tap == KK * PK.kk,
+                "load_frag walks [tap][kk][wave_m][lane][wm] by Horner's rule");
   const int stage_sz = conv_f32_stage(wchunk, nx);
 
   extern __shared__ __attribute__((aligned(16))) float lds[];

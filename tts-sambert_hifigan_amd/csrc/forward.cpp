@@ -200,8 +200,8 @@ int launch_layer(Launcher& ln, const Layer& L, ConvParams& p, bool ups, int64_t 
        (h->small_tile != 0 &&
         (int64_t)n_tiles_of(*pk) * pk->m_tiles * B * ln.conc < hfg::kSmallGridBlocks)))
     pk = &L.pk[1];
-  p.w = h->packed_dev + pk->w_off;
-  p.bias = h->packed_dev + pk->b_off;
+  p.w = h->packed_dev + pk->w.off;
+  p.bias = h->packed_dev + pk->b.off;
   p.n_chunks = pk->n_chunks;
   const char* name = nullptr;
   ln.begin(flop, bytes);
@@ -300,9 +300,9 @@ int run_resblock(Launcher& ln, const RbFused& rb, const Dims& d, const float* x,
     p.bs = (int64_t)C * Lt;
     p.L = (int)Lt;
     p.len = d.lens;
-    p.w = reinterpret_cast<const __bf16*>(h->packed_dev + rb.w_off);
-    p.w_bytes = (int)(rb.w_len * sizeof(float));
-    p.bias = h->packed_dev + rb.b_off + (size_t)c0 * C;
+    p.w = reinterpret_cast<const __bf16*>(h->packed_dev + rb.w.off);
+    p.w_bytes = (int)(rb.w.len * sizeof(float));
+    p.bias = h->packed_dev + rb.b.off + hfg::pack_bias_convs(c0, C);
     p.n_conv = c1 - c0;
     p.conv0 = c0;
     p.n_conv_stream = n_all;
@@ -331,7 +331,7 @@ int run_resblock(Launcher& ln, const RbFused& rb, const Dims& d, const float* x,
     if (h->rb_persist && per_cu == 1 && !(last && post) && !rb2)
       p.persist = std::max(1, h->n_cu / (h->rb_persist == 1 ? h->halves : 1));
     double bytes =
-        4.0 * B * Lt * C * ((last && (out.mode & 1)) ? 3 : 2) + 4.0 * (double)rb.w_len;
+        4.0 * B * Lt * C * ((last && (out.mode & 1)) ? 3 : 2) + 4.0 * (double)rb.w.len;
     if (last && post) {
       // the stage output is exact on the centre plus conv_post's radius on either side
       p.halo = rb.halo_post;
@@ -378,8 +378,8 @@ int run_ups(Launcher& ln, const Layer& L, const Dims& in, Src x, const Dims& out
       q.L = (int)Lin;
       q.T = (int)Lin;
       q.len_in = in.lens;
-      q.w = reinterpret_cast<const __bf16*>(h->packed_dev + L.wf_off);
-      q.bias = h->packed_dev + L.bf_off;
+      q.w = reinterpret_cast<const __bf16*>(h->packed_dev + L.wf.off);
+      q.bias = h->packed_dev + L.bf.off;
       q.y = y.p;
       q.y_bs = (int64_t)L.C_out * Lout;
       q.C_out = L.C_out;
@@ -441,12 +441,12 @@ int run_thin(Launcher& ln, const Stage& st, const Dims& d, const float* X, Act o
     p.kt[q] = L.k;
     p.dil[q] = L.dil;
     p.ew[q] = L.ew;
-    p.w_off[q] = (int)st.thin_w_off[e];
+    p.w_off[q] = (int)st.thin_w[e].off;
     flop += 2.0 * C * C * L.k * (double)Lt * B;
     wbytes += 4.0 * C * C * L.k;
   }
   // the kernel indexes biases as [conv][C] from this launch's first conv
-  p.bias = h->packed_dev + st.thin_b_off + (size_t)cv_base * C;
+  p.bias = h->packed_dev + st.thin_b.off + hfg::pack_bias_convs(cv_base, C);
   p.halo = halo;
   p.W = (st.thin_mfma ? hfg::thin_mfma_window(C) : hfg::thin_window(C)) - 2 * halo;
   p.y = out.p;
@@ -454,8 +454,8 @@ int run_thin(Launcher& ln, const Stage& st, const Dims& d, const float* X, Act o
   p.amax_out = out.amax;
   if (st.thin_mfma) {
     const int base = st.thin_m_conv[cv_base];
-    p.wm = reinterpret_cast<const __bf16*>(h->packed_dev + st.thin_m_off) + base / 2;
-    p.wm_bytes = (int)st.thin_m_bytes - base;
+    p.wm = reinterpret_cast<const __bf16*>(h->packed_dev + st.thin_m.off) + base / 2;
+    p.wm_bytes = (int)(st.thin_m.len * sizeof(float)) - base;
     for (int e = st.thin_conv0[j0]; e < st.thin_conv0[j1]; ++e)
       p.wm_off[e - cv_base] = st.thin_m_conv[e] - base;
   }
@@ -704,7 +704,7 @@ int forward_part(Launcher& ln, const FwdIo& io, const std::vector<int64_t>& L, c
         hipError_t e = hipMemsetAsync(wav, 0, sizeof(float) * (size_t)(B * d.L), stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(wav)");
       }
-      const PostFuse pf{h->packed_dev + Lp.pk[0].w_off, h->packed_dev + Lp.pk[0].b_off, wav,
+      const PostFuse pf{h->packed_dev + Lp.pk[0].w.off, h->packed_dev + Lp.pk[0].b.off, wav,
                         post_slope_of(h)};
       rc = run_mrf(ln, st, d, x, bufs, cur, -1, &pf);
       return rc ? rc : sl.end();
@@ -718,8 +718,8 @@ int forward_part(Launcher& ln, const FwdIo& io, const std::vector<int64_t>& L, c
   const char* name = nullptr;
   ln.begin(2.0 * Lp.C_in * 7 * (double)d.L * B, 4.0 * B * d.L * (Lp.C_in + 1));
   hipError_t e = hfg::launch_conv_post(cur.p, (int64_t)Lp.C_in * d.L, Lp.C_in, (int)d.L,
-                                       h->packed_dev + Lp.pk[0].w_off,
-                                       h->packed_dev + Lp.pk[0].b_off, wav, d.lens,
+                                       h->packed_dev + Lp.pk[0].w.off,
+                                       h->packed_dev + Lp.pk[0].b.off, wav, d.lens,
                                        post_slope_of(h), (int)B, stream, &name);
   ln.end(name);
   if (e != hipSuccess) return fail(HFG_EIO, "launch conv_post: %s", hipGetErrorString(e));

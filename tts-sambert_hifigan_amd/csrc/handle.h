@@ -56,11 +56,14 @@ void sched_apply(const char* knob, bool* v);
 
 enum LayerKind { L_CONV, L_UPS, L_POST };
 
-// One packing of a layer's weights and per-row biases for one tile of its kernel: offsets
-// and lengths in floats into the packed buffer.
+// A region of the packed buffer, in floats; its length is its layout's size (pack_layout.h).
+// len == 0: absent
+struct PackRegion { size_t off = 0, len = 0; };
+
+// One packing of a layer's weights and per-row biases for one tile of its kernel.
 struct Packing {
   int tile, m_tiles, n_chunks;
-  size_t w_off, w_len, b_off, b_len;
+  PackRegion w, b;
 };
 
 struct Layer {
@@ -73,11 +76,11 @@ struct Layer {
   int ew = 0;        // f16x3: power-of-two exponent of this layer's weight packing
   // [0]: the layer's own tile; [1]: split-precision layers' second packing for the small-grid
   // tile (kBf16x3SmallTile), tile -1: none
-  Packing pk[2] = {{0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0}};
+  Packing pk[2] = {{0, 0, 0, {}, {}}, {-1, 0, 0, {}, {}}};
   // bf16x3 upsamplers with k = 2u: the output-frame kernel (ups_bf16x3.hip) on its own
   // packing, -1: none
   int ups_cfg = -1, m_tiles_f = 0;
-  size_t wf_off = 0, bf_off = 0;
+  PackRegion wf, bf;
 };
 
 // f16x3, bf16x3 and bf16w run the split-operand MFMA kernels (f16x3 and bf16w in the f16
@@ -99,8 +102,8 @@ struct ProfRec {
   int fwd, part, seq;  // forward call, batch half (0/1), launch index inside that half
 };
 
-// One ResBlock run by resblock_bf16x3 (whole block per launch): its packed A stream
-// [wave_m][conv][group][tap][plane][lane][8] and biases [conv][C] in the packed buffer.
+// One ResBlock run by resblock_bf16x3 (whole block per launch): its packed A stream (rb_nest,
+// pack_layout.h) and biases [conv][C] in the packed buffer.
 struct RbFused {
   std::vector<int> convs;     // layer indices in execution order conv1_0, conv2_0, conv1_1, ...
   bool fused = false;         // this ResBlock runs as one resblock_bf16x3 launch
@@ -113,7 +116,7 @@ struct RbFused {
   // last launch is then exact on conv_post's radius more on either side
   bool post = false;
   int halo_post = 0, W_post = 0;
-  size_t w_off = 0, w_len = 0, b_off = 0, b_len = 0;  // in floats
+  PackRegion w, b;
 };
 
 struct Stage {
@@ -127,12 +130,11 @@ struct Stage {
   std::vector<int> thin_convs;   // layer indices: conv1_0, conv2_0, conv1_1, ... per ResBlock
   std::vector<int> thin_conv0;   // ResBlock j runs thin_convs[thin_conv0[j] .. thin_conv0[j+1])
   std::vector<int> thin_halo;    // per ResBlock receptive-field radius
-  std::vector<size_t> thin_w_off;  // per conv, floats into the packed buffer ([tap][ci][co])
-  size_t thin_b_off = 0;           // [conv][C]
-  // bf16x3: the MFMA kernel's A stream [conv][step][plane][lane][8] (mrf_thin_mfma.hip)
+  std::vector<PackRegion> thin_w;  // per conv (thin_nest, pack_layout.h)
+  PackRegion thin_b;               // [conv][C]
+  // bf16x3: the MFMA kernel's A stream, the convs of thin_mfma_nest one after another
   bool thin_mfma = false;
-  size_t thin_m_off = 0;           // floats into the packed buffer
-  size_t thin_m_bytes = 0;
+  PackRegion thin_m;
   std::vector<int> thin_m_conv;    // byte offset of each conv inside the stream
 };
 

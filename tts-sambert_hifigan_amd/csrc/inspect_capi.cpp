@@ -25,15 +25,14 @@ const SchedKnob* sched_knob(const char* name) {
 
 int commit_if_dirty(hfg_handle* h) { return h->dirty ? do_commit(h) : HFG_OK; }
 
-// How a copy-out ends: pending weights committed, then w_len weights and b_len biases of the
-// packed host image (offsets in floats) into out[cap]
-int copy_packed(hfg_handle* h, float* out, size_t cap, size_t w_off, size_t w_len, size_t b_off,
-                size_t b_len) {
+// How a copy-out ends: pending weights committed, then the weights w and the biases b of the
+// packed host image into out[cap]
+int copy_packed(hfg_handle* h, float* out, size_t cap, const PackRegion& w, const PackRegion& b) {
   int rc = commit_if_dirty(h);
   if (rc) return rc;
-  if (cap < w_len + b_len) return fail(HFG_EINVAL, "output buffer too small");
-  memcpy(out, h->packed_host.data() + w_off, sizeof(float) * w_len);
-  memcpy(out + w_len, h->packed_host.data() + b_off, sizeof(float) * b_len);
+  if (cap < w.len + b.len) return fail(HFG_EINVAL, "output buffer too small");
+  memcpy(out, h->packed_host.data() + w.off, sizeof(float) * w.len);
+  memcpy(out + w.len, h->packed_host.data() + b.off, sizeof(float) * b.len);
   return HFG_OK;
 }
 
@@ -161,15 +160,13 @@ int hfg_debug_packed_layer(hfg_handle* h, const char* mod, float* out, size_t ca
     if (L.mod != name) continue;
     if (which == 2) {
       if (L.ups_cfg < 0) return fail(HFG_EINVAL, "%s has no output-frame packing", name.c_str());
-      const hfg::UpsCfg& tf = hfg::kUpsCfgs[L.ups_cfg];
-      const size_t w_len = (size_t)L.m_tiles_f * (L.C_in / 16) * 8 * tf.MT() * 16 / 2;
-      const size_t b_len = (size_t)L.C_out;
       if (info) {
         const int64_t v[10] = {L.kind, (int64_t)L.C_out * L.s / 2, 2, L.ups_cfg, L.m_tiles_f,
-                               L.C_in / 16, (int64_t)w_len, (int64_t)b_len, 16, tf.MT()};
+                               L.C_in / 16, (int64_t)L.wf.len, (int64_t)L.bf.len, 16,
+                               hfg::kUpsCfgs[L.ups_cfg].MT()};
         std::copy_n(v, 10, info);
       }
-      return out ? copy_packed(h, out, cap, L.wf_off, w_len, L.bf_off, b_len) : HFG_OK;
+      return out ? copy_packed(h, out, cap, L.wf, L.bf) : HFG_OK;
     }
     const Packing& pk = L.pk[which];
     if (which == 1 && pk.tile < 0)
@@ -181,14 +178,14 @@ int hfg_debug_packed_layer(hfg_handle* h, const char* mod, float* out, size_t ca
       info[3] = pk.tile;
       info[4] = pk.m_tiles;
       info[5] = pk.n_chunks;
-      info[6] = (int64_t)pk.w_len;
-      info[7] = (int64_t)pk.b_len;
+      info[6] = (int64_t)pk.w.len;
+      info[7] = (int64_t)pk.b.len;
       info[8] = L.CK;
       info[9] = L.kind == L_POST ? 0
                 : L.prec == 1    ? hfg::kBf16x3Tiles[pk.tile].MT()
                                  : kTiles[pk.tile].MT();
     }
-    return out ? copy_packed(h, out, cap, pk.w_off, pk.w_len, pk.b_off, pk.b_len) : HFG_OK;
+    return out ? copy_packed(h, out, cap, pk.w, pk.b) : HFG_OK;
   }
   return fail(HFG_EINVAL, "unknown layer '%s'", mod);
 }
@@ -224,9 +221,9 @@ int hfg_debug_packed_resblock(hfg_handle* h, int stage, int j, float* out, size_
   info[3] = (int64_t)rb.convs.size();
   info[4] = rb.halo;
   info[5] = rb.W;
-  info[6] = (int64_t)rb.w_len;
-  info[7] = (int64_t)rb.b_len;
-  return out ? copy_packed(h, out, cap, rb.w_off, rb.w_len, rb.b_off, rb.b_len) : HFG_OK;
+  info[6] = (int64_t)rb.w.len;
+  info[7] = (int64_t)rb.b.len;
+  return out ? copy_packed(h, out, cap, rb.w, rb.b) : HFG_OK;
 }
 
 int hfg_debug_thin_window(int C, int mfma) {
@@ -312,9 +309,9 @@ int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen) {
     js.begin_object().string("mod", L.mod).integer("kind", L.kind).integer("prec", L.prec);
     js.integer("tile", pk.tile).integer("m_tiles", pk.m_tiles).integer("n_chunks", pk.n_chunks);
     js.integer("CK", L.CK).integer("ew", L.ew);
-    js.integers("w", {(long long)pk.w_off, (long long)pk.w_len, (long long)pk.b_off, (long long)pk.b_len});
-    js.integers("small", {ps.tile, ps.m_tiles, ps.n_chunks, (long long)ps.w_off, (long long)ps.b_off});
-    js.integers("frames", {L.ups_cfg, L.m_tiles_f, (long long)L.wf_off, (long long)L.bf_off});
+    js.integers("w", {(long long)pk.w.off, (long long)pk.w.len, (long long)pk.b.off, (long long)pk.b.len});
+    js.integers("small", {ps.tile, ps.m_tiles, ps.n_chunks, (long long)ps.w.off, (long long)ps.b.off});
+    js.integers("frames", {L.ups_cfg, L.m_tiles_f, (long long)L.wf.off, (long long)L.bf.off});
     js.end_object();
   }
   js.end_array().key("stages").begin_array();
@@ -324,11 +321,13 @@ int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen) {
     js.integers("conv1", st.conv1).integers("conv2", st.conv2);
     if (st.thin) {
       js.integers("thin_convs", st.thin_convs).integers("thin_conv0", st.thin_conv0);
-      js.integers("thin_halo", st.thin_halo).integers("thin_w_off", st.thin_w_off);
-      js.integer("thin_b_off", (long long)st.thin_b_off);
+      std::vector<size_t> w_off;
+      for (const PackRegion& r : st.thin_w) w_off.push_back(r.off);
+      js.integers("thin_halo", st.thin_halo).integers("thin_w_off", w_off);
+      js.integer("thin_b_off", (long long)st.thin_b.off);
     }
     if (st.thin && st.thin_mfma) {
-      js.integers("thin_m", {(long long)st.thin_m_off, (long long)st.thin_m_bytes});
+      js.integers("thin_m", {(long long)st.thin_m.off, (long long)(st.thin_m.len * sizeof(float))});
       js.integers("thin_m_conv", st.thin_m_conv);
     }
     js.key("rbs").begin_array();
@@ -339,7 +338,7 @@ int hfg_debug_plan(hfg_handle* h, char* buf, size_t buflen) {
         js.integer("wm", rb.wm).integer("halo", rb.halo).integer("W", rb.W);
         js.integer("split", rb.split);
         if (rb.split) js.integers("parts", {rb.halo_p[0], rb.halo_p[1], rb.W_p[0], rb.W_p[1]});
-        js.integers("w", {(long long)rb.w_off, (long long)rb.w_len, (long long)rb.b_off, (long long)rb.b_len});
+        js.integers("w", {(long long)rb.w.off, (long long)rb.w.len, (long long)rb.b.off, (long long)rb.b.len});
         js.integer("post", rb.post);  // conv_post fused into this launch, for a call that allows it
       }
       js.end_object();

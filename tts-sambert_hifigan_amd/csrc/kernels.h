@@ -48,7 +48,7 @@ struct ConvParams {
   int C_in, L_in;
   const int32_t* len_in;   // per-item valid input length (device, [B]) or null = L_in
   const int32_t* len_out;  // per-item valid output length (device, [B]) or null = N / L_out
-  const float* w;    // packed weights (layouts: pack.cpp)
+  const float* w;    // packed weights (pack_layout.h)
   const float* bias; // per GEMM row m, length >= m_tiles * MT
   float* y;          // output [B][M][N] (regular) or [B][C_out][L_out] (UPS)
   int64_t y_bs;
@@ -202,7 +202,7 @@ struct UpsParams {
   int C_in, L;           // channels, row length (L % 4 == 0)
   int T;                 // frames (GEMM columns) per item, <= L
   const int32_t* len_in; // per-item valid frames (device, [B]) or null = T
-  const __bf16* w;       // packed [m_tile][g][class][tap][plane][wave_m][wm][lane][8]
+  const __bf16* w;       // packed A slabs (ups_pack, pack_layout.h)
   const float* bias;     // [C_out]
   float* y;              // [B][C_out][L_out]
   int64_t y_bs;
@@ -233,7 +233,7 @@ struct RbParams {
   int64_t bs;            // batch stride of x and mrf (C * L)
   int L;                 // row length
   const int32_t* len;    // per-item valid length (device, [B]) or null = L
-  const __bf16* w;       // packed A stream [wave_m][conv][group][tap][plane][lane][8]
+  const __bf16* w;       // packed A stream (rb_pack, pack_layout.h)
   int w_bytes;           // its size (buffer descriptor range)
   const float* bias;     // [conv][C]
   int n_conv;            // convs of this launch (even), order conv1_0, conv2_0, conv1_1, ...
@@ -250,7 +250,7 @@ struct RbParams {
   // fused conv_post + tanh (C = 32, the last MRF write; L % 4 == 0): wav [B][L] written on the
   // centre [halo, halo + W) of each window, mrf not stored; halo includes the conv's radius 3.
   // Windows past an item's length write nothing (the host zeroes wav first).  Null: off
-  const float* post_w;   // conv_post weight [C][7] fp32
+  const float* post_w;   // conv_post weight (conv_post_nest, pack_layout.h) fp32
   const float* post_b;   // conv_post bias [1]
   float* wav;
   int batch;             // items (set by launch_resblock_bf16x3)
@@ -281,7 +281,7 @@ hipError_t launch_resblock2_bf16x3(int C, int nwin, int wm, int kt, int fmt, int
 
 // ---- whole MRF per launch for thin stages, C <= 16 (mrf_thin.hip) ----
 // All ResBlocks of one MRF on a time window in LDS, packed-fp32 VALU dot products (exact
-// fp32 products).  Weights packed per conv [tap][ci][co] (fp32), biases [conv][C].
+// fp32 products).  Weights packed per conv (thin_nest, pack_layout.h), biases [conv][C].
 constexpr int kThinMarg = 64;      // spare operand columns per side: every (k-1)/2*d must fit
 constexpr int kThinMaxRes = 8;
 constexpr int kThinMaxConv = 64;
@@ -298,7 +298,7 @@ struct ThinParams {
   int halo, W;               // largest ResBlock radius, output columns per block
   float* y;                  // [B][C][L] <- (sum of the ResBlocks' outputs) / div
   float div;
-  // bf16x3 MFMA variant (mrf_thin_mfma.hip): A stream [conv][step][plane][lane][8] bf16
+  // bf16x3 MFMA variant (mrf_thin_mfma.hip): A stream of thin_mfma_pack (pack_layout.h)
   const __bf16* wm;          // this launch's stream
   int wm_bytes;              // its size (buffer descriptor range)
   int wm_off[kThinMaxConv];  // byte offset of each conv's first k-step
@@ -378,4 +378,5 @@ hipError_t launch_stage_lengths(const int32_t* lens, int B, const StageLenParams
 
 }  // namespace hfg
 
+#include "pack_layout.h"
 #include "lds_layout.h"

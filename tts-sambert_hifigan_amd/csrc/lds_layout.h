@@ -1,7 +1,8 @@
 // lds_layout.h — the dynamic-LDS carve-up of every kernel family, stated once.  A kernel takes
 // its offsets and strides from its layout, its launcher (and the plan, where it consults the
 // size) takes the total from the same value: a row or a pad added here moves both sides.
-// Included at the end of kernels.h (it needs the tile configurations declared there).
+// Included at the end of kernels.h, after pack_layout.h (it needs the tile configurations
+// declared there, and the global slabs whose LDS copies it places).
 //
 // A layout whose inputs are all template arguments is a plain struct of ints filled by a
 // constexpr function, evaluated at compile time in the kernel.  A term with a runtime input
@@ -30,7 +31,7 @@ constexpr size_t epi_stage_bytes(int threads, int WN) {
 // plane row per staging task, and the m-tile's bias copy past the windows and the staging.
 constexpr int kBf16x3XRow = 16;  // bf16 per staged row: 16 channels (32 B)
 struct ConvBf16x3Lds {
-  int slab;      // bf16 per chunk slab: TPC taps x (hi, lo) x MT rows x 16 channels
+  int slab;      // bf16 per chunk slab: the global slab (pack_layout.h), copied whole
   int xw_max;    // widest window the instantiation stages (sizes its staging registers)
   int xq;        // staging tasks per thread: (row, 8-channel half) pairs of xw_max rows
   int xrows;     // AREG: rows of a plane, one per staging task (>= xw_max)
@@ -51,7 +52,7 @@ __host__ __device__ constexpr int bf16x3_xplane(int xw) { return (xw * kBf16x3XR
 constexpr ConvBf16x3Lds conv_bf16x3_lds(const Bf16x3Cfg& t, int kt_max, int xw) {
   ConvBf16x3Lds l{};
   const int nt = t.threads();
-  l.slab = t.TPC * 2 * t.WAVES_M * t.WM * 64 * 8;
+  l.slab = conv_bf16x3_pack(t).slab;
   l.xw_max = t.NTILE() + ((kt_max - 1) * kMaxDil < kBf16x3MaxHalo ? (kt_max - 1) * kMaxDil
                                                                    : kBf16x3MaxHalo);
   l.xq = (2 * l.xw_max + nt - 1) / nt;
@@ -72,7 +73,7 @@ constexpr int bf16x3_xw(const Bf16x3Cfg& t, int kt, int dil) { return t.NTILE() 
 // ---- ups_bf16x3 (ups_bf16x3.hip) ----
 // [2 A slabs][2 input windows x (hi, lo) planes]; all bytes
 struct UpsLds {
-  int slab;    // class x tap x plane x rows of one 16-channel group
+  int slab;    // one 16-channel group's global slab (pack_layout.h), copied whole
   int xr;      // staged frames: [m0 - 4, m0 + NTILE + 4), quad-aligned
   int xplane;  // one bf16 plane [frame][16 ch]
   int xbuf;    // hi + lo
@@ -81,7 +82,7 @@ struct UpsLds {
 };
 constexpr UpsLds ups_lds(const UpsCfg& t) {
   UpsLds l{};
-  l.slab = 2 * 2 * 2 * t.WAVES_M * t.WM * 1024;
+  l.slab = ups_pack(t).slab;
   l.xr = t.NTILE() + 8;
   l.xplane = l.xr * 32;
   l.xbuf = 2 * l.xplane;
@@ -155,10 +156,8 @@ constexpr ThinMfmaLds thin_mfma_lds(int C, int nwin) {
 }
 
 // ---- conv1d_mfma_f32 (conv_kernels.hip): two pipeline stages of [weight slab][input rows];
-// floats.  The LDS-staged epilogue runs only where its staging fits under them. ----
-__host__ __device__ constexpr int conv_f32_wchunk(int MT, int CK, int kt) {
-  return MT * CK * kt;  // one weight slab: MT rows x CK channels x kt taps
-}
+// floats; the weight slab is the global one (conv_f32_slab, pack_layout.h).  The LDS-staged
+// epilogue runs only where its staging fits under them. ----
 __host__ __device__ constexpr int conv_f32_nx(int CK, int xw) {
   return CK * xw;       // staged input: CK rows of the window
 }
@@ -167,12 +166,12 @@ __host__ __device__ constexpr int conv_f32_stage(int wchunk, int nx) {
   return wchunk + ((nx + 3) & ~3);
 }
 constexpr size_t conv_f32_lds_total(int MT, int CK, int kt, int xw) {
-  return sizeof(float) * 2 * (size_t)conv_f32_stage(conv_f32_wchunk(MT, CK, kt), conv_f32_nx(CK, xw));
+  return sizeof(float) * 2 * (size_t)conv_f32_stage(conv_f32_slab(MT, CK, kt), conv_f32_nx(CK, xw));
 }
 
 // ---- conv_post_tanh (conv_kernels.hip): [C x 7 weights, rounded up to 16 B][kConvPostCB
 // input rows of a 256-sample tile plus its 6 halo columns]; floats ----
-constexpr int kConvPostTile = 256, kConvPostTaps = 7;
+constexpr int kConvPostTile = 256;  // (kConvPostTaps: pack_layout.h)
 constexpr int kConvPostXw = kConvPostTile + kConvPostTaps - 1;  // staged columns per row
 // the input rows: past the weights
 __host__ __device__ constexpr int conv_post_x_off(int C) { return (C * kConvPostTaps + 3) & ~3; }

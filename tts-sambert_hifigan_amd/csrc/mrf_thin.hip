@@ -20,7 +20,7 @@
 // columns, every channel of the ResBlock state xr, the MRF sum and the conv accumulator in
 // registers.  The conv operand (lrelu of the previous conv's output, zero outside [0, len))
 // is one LDS buffer [C][MARG + NWIN + MARG], rewritten after every conv.  Weights are
-// uniform across the block: packed per conv as [tap][ci][co] and read with scalar loads
+// uniform across the block: packed per conv (thin_nest, pack_layout.h) and read with scalar loads
 // (s_load_dwordx16 of the C output channels of one (tap, ci)).
 //
 // Receptive field: edge columns turn to garbage one conv radius at a time; the block
@@ -55,6 +55,8 @@ mrf_thin(const ThinParams p) {             // lgkmcnt(0) waits on the scalar wei
   static_assert(LY.total <= (int)kMaxLdsBytes, "LDS");
   constexpr int RS = LY.rs;               // LDS row stride (floats)
   constexpr int CG = C < 2 ? C : 2;       // input channels per scalar-load group
+  static_assert(thin_nest(C, 1).d[0].stride == C * C && thin_nest(C, 1).d[1].stride == C,
+                "run_conv walks the packed [tap][ci][co] (pack_layout.h) by Horner's rule");
   extern __shared__ __attribute__((aligned(16))) float op[];
 
   const int tid = threadIdx.x;

@@ -21,8 +21,8 @@
 // [row = column][16 channels] per plane; rows are 32 B whose two 16-B halves are swapped
 // when bit 3 of the row is set, so the 16 lanes of a B-fragment read (16 B each,
 // consecutive rows) hit distinct banks.  Weights (A fragments) are host-packed per
-// (conv, k-step) as [plane][lane][8] = 2 KB and loaded from L2 by buffer loads (uniform
-// across the block) into registers one conv ahead.
+// (conv, k-step) as 2 KB (thin_mfma_pack, pack_layout.h) and loaded from L2 by buffer loads
+// (uniform across the block) into registers one conv ahead.
 // f16x3: every operand the block writes is scaled by the power of two of the block's largest
 // |value| (posted per wave before one extra barrier per conv); the conv result is unscaled
 // by 2^-(e_x + e_w) before its bias.
@@ -93,10 +93,11 @@ mrf_thin_mfma(const ThinParams p) {
     return row * RB + ((((ch >> 3) ^ (row >> 3)) & 1) << 4) + (ch & 7) * 2;
   };
 
-  // ---- A stream: buffer loads of [conv][step][plane][lane][8] ----
+  // ---- A stream: buffer loads, strides of thin_mfma_pack (pack_layout.h) ----
+  constexpr ThinMfmaPack PK = thin_mfma_pack();
   const __amdgpu_buffer_rsrc_t wrs =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.wm, 0, p.wm_bytes, 0x00020000);
-  const int a_lane = lane * 16;
+  const int a_lane = lane * PK.lane;
 
   // operand <- lrelu(v) * sc, zero outside [0, len), hi/lo split
   auto write_operand = [&](const floatx4 (&v)[NCT], char* buf, float sc) {
@@ -154,10 +155,10 @@ mrf_thin_mfma(const ThinParams p) {
     const int wo = p.wm_off[cv];
 #pragma unroll
     for (int s = 0; s < MS; ++s) {
-      const int so = wo + min(s, steps - 1) * 2048;
+      const int so = wo + min(s, steps - 1) * PK.step;
       a0[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane, so, 0));
       a1[s] =
-          __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane + 1024, so, 0));
+          __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane + PK.plane, so, 0));
     }
   };
   // acc = bias + W_cv * operand (f16x3: unscaled by inv first), with (a0, a1) = conv cv's A

@@ -34,14 +34,11 @@ int split_fmt(int dtype) {
 }
 size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
-// Packed-buffer offsets: take(len) is the next region's offset, 64-float aligned.
+// Packed-buffer regions one after another, each 64-float aligned; len: its layout's size
+// (pack_layout.h).
 struct Bump {
   size_t off = 0;
-  size_t take(size_t len) {
-    const size_t at = off;
-    off += (len + 63) & ~(size_t)63;
-    return at;
-  }
+  PackRegion take(size_t len) { return {std::exchange(off, off + ((len + 63) & ~(size_t)63)), len}; }
 };
 
 }  // namespace
@@ -177,8 +174,8 @@ int plan_layers(hfg_handle* h, Bump& off) {
   for (auto& L : h->layers) {
     Packing& pk = L.pk[0];
     if (L.kind == L_POST) {
-      pk.w_off = off.take(pk.w_len = (size_t)L.C_in * 7);
-      pk.b_off = off.take(pk.b_len = 1);
+      pk.w = off.take(hfg::conv_post_pack_floats(L.C_in));
+      pk.b = off.take(hfg::pack_bias_convs(1, L.C_out));
       continue;
     }
     if (split_dtype(h->cfg.dtype) && hfg::bf16x3_tile_for_rows(L.M) >= 0 &&
@@ -189,10 +186,9 @@ int plan_layers(hfg_handle* h, Bump& off) {
       auto packing = [&](int tile) {
         const hfg::Bf16x3Cfg& t = hfg::kBf16x3Tiles[tile];
         Packing p{tile, (int)ceil_div(L.M, t.MT()),
-                  (int)(ceil_div(L.C_in, L.CK) * ceil_div(L.KT, t.TPC)), 0, 0, 0, 0};
-        // slabs of TPC taps x (hi, lo) x MT rows x 16 channels, in bf16: two per float
-        p.w_off = off.take(p.w_len = (size_t)p.m_tiles * p.n_chunks * t.TPC * 2 * t.MT() * 16 / 2);
-        p.b_off = off.take(p.b_len = (size_t)p.m_tiles * t.MT());
+                  hfg::conv_bf16x3_groups(L.C_in) * hfg::conv_bf16x3_tap_groups(t, L.KT), {}, {}};
+        p.w = off.take(hfg::conv_bf16x3_pack_floats(t, p.m_tiles, p.n_chunks));
+        p.b = off.take(hfg::pack_bias_rows(p.m_tiles, t.MT()));
         return p;
       };
       int tile = hfg::bf16x3_tile_for_rows(L.M);
@@ -218,9 +214,8 @@ int plan_layers(hfg_handle* h, Bump& off) {
           const hfg::UpsCfg& tf = hfg::kUpsCfgs[cfg];
           L.ups_cfg = cfg;
           L.m_tiles_f = rows_f / tf.MT();
-          // bf16: m-tiles x groups x (class, tap, plane) x rows x 16 ch
-          L.wf_off = off.take((size_t)L.m_tiles_f * (L.C_in / 16) * 8 * tf.MT() * 16 / 2);
-          L.bf_off = off.take(L.C_out);
+          L.wf = off.take(hfg::ups_pack_floats(tf, L.m_tiles_f, L.C_in / 16));
+          L.bf = off.take(hfg::pack_bias_convs(1, L.C_out));
         }
       }
       continue;
@@ -235,8 +230,8 @@ int plan_layers(hfg_handle* h, Bump& off) {
     L.CK = hfg::ck_for(hfg::dispatch_kt(L.KT), pk.tile);
     pk.m_tiles = (int)ceil_div(L.M, t.MT());
     pk.n_chunks = (int)ceil_div(L.C_in, L.CK);
-    pk.w_off = off.take(pk.w_len = (size_t)pk.m_tiles * pk.n_chunks * t.MT() * L.CK * L.KT);
-    pk.b_off = off.take(pk.b_len = (size_t)pk.m_tiles * t.MT());
+    pk.w = off.take(hfg::conv_f32_pack_floats(t, L.CK, L.KT, pk.m_tiles, pk.n_chunks));
+    pk.b = off.take(hfg::pack_bias_rows(pk.m_tiles, t.MT()));
   }
   return HFG_OK;
 }
@@ -299,8 +294,8 @@ void plan_resblocks(hfg_handle* h, Bump& off) {
       rb.halo_post = (rb.split ? rb.halo_p[1] : rb.halo) + post;
       rb.W_post = window_width(nwin, rb.halo_post);
       rb.post = rb.post && rb.halo_post >= 4 && rb.W_post;
-      rb.w_off = off.take(rb.w_len = (size_t)n * C * C * rb.kt);  // bf16 hi + lo = one float each
-      rb.b_off = off.take(rb.b_len = (size_t)n * C);
+      rb.w = off.take(hfg::rb_pack_floats(C, rb.kt, n));
+      rb.b = off.take(hfg::pack_bias_convs(n, C));
       st.rbs[j] = std::move(rb);
     }
   }
@@ -333,8 +328,8 @@ void plan_thin(hfg_handle* h, Bump& off) {
     st.thin_convs = convs;
     st.thin_conv0 = conv0;
     st.thin_halo = halos;
-    for (int cv : convs) st.thin_w_off.push_back(off.take((size_t)h->layers[cv].k * C * C));
-    st.thin_b_off = off.take((size_t)n_conv * C);
+    for (int cv : convs) st.thin_w.push_back(off.take(hfg::thin_pack_floats(C, h->layers[cv].k)));
+    st.thin_b = off.take(hfg::pack_bias_convs(n_conv, C));
     // bf16x3: the MFMA variant when every conv's zero-padded last k-step stays in the
     // operand margin
     const int tps = 32 / C, nwin_m = hfg::thin_mfma_window(C);
@@ -342,18 +337,15 @@ void plan_thin(hfg_handle* h, Bump& off) {
     size_t bytes = 0;
     for (int cv : convs) {
       const Layer& Lc = h->layers[cv];
-      const int steps = (Lc.k + tps - 1) / tps;
+      const int steps = hfg::thin_mfma_steps(C, Lc.k);
       if (((steps * tps - 1) - (Lc.k - 1) / 2) * Lc.dil > hfg::kThinMarg ||
           steps > hfg::kThinMfmaMaxSteps)
         mf = false;
       st.thin_m_conv.push_back((int)bytes);
-      bytes += (size_t)steps * 2048;
+      bytes += hfg::thin_mfma_conv_bytes(C, Lc.k);
     }
     st.thin_mfma = mf;
-    if (mf) {
-      st.thin_m_bytes = bytes;
-      st.thin_m_off = off.take(bytes / 4);
-    }
+    if (mf) st.thin_m = off.take(hfg::pack_floats_of_bytes(bytes));
   }
 }
 

@@ -20,8 +20,8 @@
 // current conv's B operand lives in LDS as bf16 hi/lo planes [group][plane][col][16]
 // (one buffer, rewritten in place after a barrier).  The A operand (weights) is
 // streamed from global memory (L2/L1-resident: every block reads the same stream)
-// straight into registers two k-steps ahead; it is packed per wave row-block as
-// [wave_m][conv][group][tap][plane][lane][8] so each k-step is 2 x 1 KB coalesced.
+// straight into registers two k-steps ahead; it is packed per wave row-block (rb_pack,
+// pack_layout.h) so each k-step is 2 x 1 KB coalesced.
 //
 // Channel order inside a 16-channel group is permuted (slot 8h+e <-> channel
 // 4h + (e&3) + 8(e>>2)) so that the rows one lane holds in the accumulator layout are

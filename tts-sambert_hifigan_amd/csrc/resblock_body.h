@@ -10,8 +10,8 @@
 // The body of both kernels.  RB2 = false: the reference's ResBlock (dilation pairs,
 // resblock_bf16x3); RB2 = true: the public release's ResBlock2 (resblock2_bf16x3),
 //   for m in dilations:  x = x + conv_m(lrelu(x))
-// — the same window, operand planes, A stream ([wave_m][conv][group][tap][plane][lane][8] with
-// n_dil convs) and epilogue; x stays in its registers across the convs and is the only tensor
+// — the same window, operand planes, A stream (rb_pack, pack_layout.h, with n_dil convs) and
+// epilogue; x stays in its registers across the convs and is the only tensor
 // ever written as an operand, so a conv costs one operand rewrite instead of a pair's two.
 #if HFG_RB2
 template <int KT, int WAVES_M, int WAVES_N, int WM, int NP, int FMT>
@@ -43,7 +43,8 @@ resblock_bf16x3(const RbParams p) {
   constexpr int PS = LY.ps;                // bytes per plane: [row][8 bf16]
   constexpr int HPS = LY.hps;              // half-group (slots 0-7 | 8-15): hi, lo planes
   constexpr int GS = LY.gs;                // 16-channel group
-  constexpr int ASTEP = 2 * 64 * 16;       // bytes per k-step of one wave row-block (hi, lo)
+  constexpr RbPack PK = rb_pack();         // the A strides (pack_layout.h), bytes
+  constexpr int ASTEP = PK.step;           // bytes per k-step of one wave row-block (hi, lo)
   static_assert(LY.bias_off <= (int)kMaxLdsBytes, "operand planes");
   static_assert(C != 32 || (WM == 1 && 32 * LY.post_row * 4 <= LY.bias_off),
                 "conv_post staging fits the operand planes");
@@ -128,7 +129,7 @@ resblock_bf16x3(const RbParams p) {
   const __amdgpu_buffer_rsrc_t wrs =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
   const int a_base = wave_m * WM * QT * ASTEP;  // row tile i: + i * QT * ASTEP
-  const int a_lane = lane * 16;
+  const int a_lane = lane * PK.lane;
   bf16x8 ra_h[2][WM], ra_l[2][WM];
   auto load_a = [&](int slot, int q) {
     const int so = a_base + min(q, QT - 1) * ASTEP;
@@ -137,7 +138,7 @@ resblock_bf16x3(const RbParams p) {
       ra_h[slot][i] = __builtin_bit_cast(
           bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane, so + i * QT * ASTEP, 0));
       ra_l[slot][i] = __builtin_bit_cast(
-          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane + 1024, so + i * QT * ASTEP, 0));
+          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, a_lane + PK.plane, so + i * QT * ASTEP, 0));
     }
   };
   load_a(0, Q0);

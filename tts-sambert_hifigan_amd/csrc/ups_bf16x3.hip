@@ -21,7 +21,7 @@
 // conv1d_bf16x3<..., UPS> (tests/test_gpu_parity.py::test_ups_frames_kernel_bitwise).
 //
 // Data flow per 16-channel group g (one barrier per group):
-//   * A (weights): the host packs [m_tile][g][class][tap][plane][wave_m][wm][lane][8] bf16;
+//   * A (weights): the host packs the slabs of ups_pack (pack_layout.h);
 //     the group's slab (128 * MT_c bf16) is copied to a 2-slot LDS ring by LDS-DMA one group
 //     ahead (no VGPRs).
 //   * B (lrelu'd, split input): the tile's frames [m0, m0+NTILE) (quad-aligned, so every load
@@ -70,7 +70,11 @@ ups_bf16x3(const UpsParams p) {
   static_assert(NTILE == 64 * NW, "one (quad, 4-channel quarter) staging sub-task per lane");
   constexpr int XPLANE = LY.xplane;          // bytes per bf16 plane [frame][16 ch]
   constexpr int XBUF = LY.xbuf;              // hi + lo
+  constexpr UpsPack PK = ups_pack(UpsCfg{WAVES_M, WAVES_N, WM, WN});  // the A strides (pack_layout.h), bytes
   constexpr int SLAB = LY.slab;              // bytes: class x tap x plane x rows
+  static_assert(SLAB == PK.slab && PK.cls == 2 * PK.tap && PK.tap == 2 * PK.plane &&
+                    PK.plane == WAVES_M * WM * PK.row_tile,
+                "the fragment reads below walk [class][tap][plane][wave_m][wm] by Horner's rule");
   constexpr int PW = SLAB / 1024 / NW;       // LDS-DMA pieces per thread per slab
   static_assert(PW * 1024 * NW == SLAB, "slab must split evenly over the waves");
 
@@ -253,7 +257,7 @@ ups_bf16x3(const UpsParams p) {
 #pragma unroll
           for (int i = 0; i < WM; ++i)
             a[c][tp][pl][i] = *reinterpret_cast<const bf16x8*>(
-                as + ((((c * 2 + tp) * 2 + pl) * WAVES_M + wave_m) * WM + i) * 1024 + lane * 16);
+                as + ((((c * 2 + tp) * 2 + pl) * WAVES_M + wave_m) * WM + i) * PK.row_tile + lane * PK.lane);
     const char* xh = Xbuf + (g & 1) * XBUF;
     prio_mfma();
 #pragma unroll
