@@ -319,10 +319,13 @@ def host_plan(pkg, blk, precision="f16x3"):
 
 def _layer_windows(plan32, plan16, j, n, r_max):
     """The layer-per-launch tiles of a block: every conv is its own launch with no halo; a tile
-    of NTILE columns is its "window"."""
+    of NTILE columns is its "window".  The first split-precision conv of the f16x3 plan names
+    the split tiles (a block may mix in convs past the split kernel's reach, which run the fp32
+    kernel inside a split handle)."""
     out = []
-    L16, L32 = plan16["layers"][0], plan32["layers"][0]
-    if L16["prec"] == 1:
+    L16 = next((L for L in plan16["layers"] if L["prec"] == 1), None)
+    L32 = plan32["layers"][0]
+    if L16:
         out.append(("tile", 32 * BF16X3_TILES[L16["tile"]][4] * BF16X3_TILES[L16["tile"]][2]))
         if L16["small"][0] >= 0:
             t = BF16X3_TILES[L16["small"][0]]
@@ -331,14 +334,18 @@ def _layer_windows(plan32, plan16, j, n, r_max):
     return [Window(tag, j, 0, n, nt, 0, nt, r_max, True) for tag, nt in out]
 
 
-@functools.lru_cache(maxsize=None)
 def windows(pkg, name):
-    """Every launch geometry the case's handle can run, from hfg_debug_plan of its f16x3 and
+    """block_windows of a case of this file."""
+    return block_windows(pkg, BY_NAME[name].blk)
+
+
+@functools.lru_cache(maxsize=None)
+def block_windows(pkg, blk):
+    """Every launch geometry the block's handle can run, from hfg_debug_plan of its f16x3 and
     fp32 plans under the default schedule: the whole-block window, both parts of a split one,
     the thin kernels' (hfg_debug_thin_window), and the NTILE of the layer launches that
     FUSED_RB 0, SMALL_TILE 1 and the fp32 precision run instead."""
     assert not pkg.schedule_overrides(), "window geometry is the default schedule's"
-    blk = BY_NAME[name].blk
     p16, p32 = host_plan(pkg, blk, "f16x3"), host_plan(pkg, blk, "fp32")
     st = p16["stages"][0]
     out = []
@@ -377,18 +384,27 @@ def length_classes(w):
                               n - 1, n, n + 1, 2 * W - 1, 2 * W, 2 * W + 1, 2 * W + h + 2)))
 
 
-def max_length(pkg, name):
-    """L <= 2 nwin + 64 of the case's largest window; C = 256 / 512: <= 600 columns."""
-    if BY_NAME[name].blk.channels >= 256:
+def block_max_length(pkg, blk):
+    """L <= 2 nwin + 64 of the block's largest window; C = 256 / 512: <= 600 columns."""
+    if blk.channels >= 256:
         return MAX_LAYER_COLS
-    return 2 * max(w.nwin for w in windows(pkg, name)) + 64
+    return 2 * max(w.nwin for w in block_windows(pkg, blk)) + 64
+
+
+def block_lengths(pkg, blk):
+    """Sorted lengths of a block: every class of every launch geometry of its handle that is a
+    length (>= 1) within block_max_length."""
+    cap = block_max_length(pkg, blk)
+    return sorted({L for w in block_windows(pkg, blk) for L in length_classes(w).values()
+                   if 1 <= L <= cap})
+
+
+def max_length(pkg, name):
+    return block_max_length(pkg, BY_NAME[name].blk)
 
 
 def lengths(pkg, name):
-    """Sorted lengths of a case: every class of every launch geometry of its handle that is a
-    length (>= 1) within max_length."""
-    cap = max_length(pkg, name)
-    return sorted({L for w in windows(pkg, name) for L in length_classes(w).values() if 1 <= L <= cap})
+    return block_lengths(pkg, BY_NAME[name].blk)
 
 
 def seams(w, length):

@@ -4,7 +4,10 @@ upsample rates and kernel sizes (exact, non-exact, k = u), ResBlock kernel sizes
 dilation lists, batch and ragged lengths.  Every configuration the C ABI accepts must
 match the oracle within the north-star 1e-4 in both precisions, with each item of a
 ragged batch bitwise equal to its solo run; a configuration it refuses must be refused
-at handle creation with a message (never at forward time, never a wrong answer)."""
+at handle creation with a message (never at forward time, never a wrong answer), and only
+where the host plan refuses the same configuration: any other exception at creation fails.
+The host refuses HOST_REFUSED of the N_CFG x 4 (seed, precision) pairs
+(test_taps_host.py::test_config_sweep_refusals_are_the_host_plans counts them on the CPU)."""
 import numpy as np
 import pytest
 import torch
@@ -12,6 +15,18 @@ import torch
 pytestmark = pytest.mark.gpu
 ATOL = 1e-4
 N_CFG = 32
+PRECISIONS = ("fp32", "f16x3", "bf16x3", "bf16w")
+HOST_REFUSED = 0   # every draw has k >= u, k <= 11, d <= 5: inside every kernel's limits
+
+
+def host_refusal(pkg, cfg, precision):
+    """The message with which the host plan (a handle without a device) refuses the
+    configuration, or None where it accepts it."""
+    try:
+        pkg.Handle(pkg.make_config(**cfg.kwargs(), precision=precision), -1)
+    except Exception as e:
+        return str(e) or repr(e)
+    return None
 
 
 def _draw(seed):
@@ -70,7 +85,7 @@ def test_random_config(pkg, dev, seed):
         refs_by[name] = [H.generator_forward(H.to_torch_state(w), cfg, mel[b:b + 1, :, :n])
                          for b, n in enumerate(lens)]
     print(f"\nseed {seed}: {cfg} lens {lens} weight_norm {wn}")
-    for precision in ("fp32", "f16x3", "bf16x3", "bf16w"):
+    for precision in PRECISIONS:
         refs = refs_by["bf16" if precision == "bf16w" else "fp32"]
         gen = pkg.HiFiGANGenerator(**cfg.kwargs(), precision=precision).eval()
         if wn:
@@ -79,10 +94,12 @@ def test_random_config(pkg, dev, seed):
         gen = gen.to(dev)
         try:
             gen.hip_handle(dev)
-        except Exception as e:  # refused configurations: at creation, with a reason
+        except Exception as e:  # refused configurations: at creation, with the host plan's reason
             msg = str(e)
             print(f"  {precision}: refused at creation: {msg}")
             assert msg, "refusal without a message"
+            host = host_refusal(pkg, cfg, precision)
+            assert host is not None, f"{precision}: the host plan accepts what creation raised on: {msg}"
             continue
         with torch.no_grad():
             out = gen(mel.to(dev), lengths=lens)
