@@ -39,6 +39,10 @@
  *     its largest stage activation (C x L) must hold fewer than 2^30 floats
  *     (V1: T <= 131071 frames, ~25 min of 22.05 kHz audio); a longer T is
  *     refused with HFG_EINVAL before any launch.
+ *   - Batch limit: B is a grid dimension of every kernel, so B must be in
+ *     [1, 65535].  hfg_forward*, hfg_reserve, hfg_mrf_forward and
+ *     hfg_resblock_forward refuse a larger B with HFG_EINVAL before any launch
+ *     or memset; hfg_workspace_bytes / hfg_mrf_workspace_bytes return 0 for it.
  *   - One handle per device.  Calls on one handle are serialised by a
  *     per-handle lock (a forward enqueues its launches, then releases it);
  *     hfg_forward with the internal workspace must not be used from two

@@ -13,12 +13,11 @@ layer (FUSED_RB = 0, the R / Tb path).
 import pytest
 import torch
 
+from argument_cases import Banded
 from oracle import config as C, prng
 
 pytestmark = pytest.mark.gpu
 
-BAND = 4096
-PATTERN = 0xA5
 PRECISIONS = ["f16x3", "fp32"]
 RAGGED = (3, 1366, [1366, 901, 37])   # B, T, valid frames per item
 
@@ -33,20 +32,6 @@ def _gen(pkg, cfg, precision, dev, seed):
     gen = pkg.HiFiGANGenerator(**cfg.kwargs(), precision=precision).eval()
     gen.load_state_dict({k: torch.from_numpy(v) for k, v in C.make_state_dict(cfg, seed).items()})
     return gen.to(dev)
-
-
-class Banded:
-    """``nbytes`` of device memory between two BAND-byte bands of PATTERN."""
-
-    def __init__(self, nbytes, dev):
-        self.nbytes = nbytes
-        self.buf = torch.full((nbytes + 2 * BAND,), PATTERN, dtype=torch.uint8, device=dev)
-        self.ptr = self.buf.data_ptr() + BAND
-
-    def assert_bands_untouched(self):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:BAND] == PATTERN).all()), "write below the workspace"
-        assert bool((self.buf[BAND + self.nbytes:] == PATTERN).all()), "write past the workspace"
 
 
 def _stream(dev):

@@ -613,6 +613,9 @@ int check_forward(const hfg_handle* h, const FwdIo& io, Shapes* sh) {
     return fail(HFG_EINVAL, "unknown mel_layout %d", o->mel_layout);
   if (io.B <= 0 || io.T <= 0) return fail(HFG_EINVAL, "B and T must be > 0 (got %lld, %lld)",
                                           (long long)io.B, (long long)io.T);
+  // the batch is a grid's y or z dimension
+  if (io.B > kMaxBatch) return fail(HFG_EINVAL, "B must be in [1, 65535] (got %lld)",
+                                    (long long)io.B);
   *sh = shapes_for(h, io.T);
   for (auto l : sh->L)
     if (l <= 0) return fail(HFG_EINVAL, "T=%lld gives an empty stage", (long long)io.T);

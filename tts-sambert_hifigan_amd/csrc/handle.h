@@ -28,6 +28,11 @@ int hip_fail(hipError_t e, const char* what);
 // How a text-returning entry ends: s and its NUL into buf, or HFG_EINVAL naming the size needed
 int return_text(const std::string& s, char* buf, size_t buflen);
 
+// The largest batch of a forward: the batch is gridDim.z of the layer convs and gridDim.y of
+// the whole-block, thin, post, combine and absmax kernels, both limited to 65535.  Every entry
+// that takes B refuses a larger one before it launches or sizes anything.
+constexpr int64_t kMaxBatch = 65535;
+
 // Schedule overrides for A/B runs and the parity suites (hfg_debug_schedule_set): a
 // process-wide table read when a handle is created.  The library reads no environment
 // variable for its schedule, so a serving process runs the default schedule whatever it

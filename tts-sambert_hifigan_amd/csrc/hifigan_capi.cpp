@@ -243,7 +243,7 @@ int64_t hfg_out_len(const hfg_handle* h, int64_t T) {
 }
 
 size_t hfg_workspace_bytes(const hfg_handle* h, int64_t B, int64_t T) {
-  if (!h || B <= 0 || T <= 0 || h->mrf_only) return 0;
+  if (!h || B <= 0 || B > kMaxBatch || T <= 0 || h->mrf_only) return 0;
   return ws_bytes_for(h, B, T);
 }
 
@@ -253,6 +253,7 @@ int hfg_reserve(hfg_handle* h, int64_t B, int64_t T) {
   std::lock_guard<std::recursive_mutex> lk(h->mu);
   if (h->device < 0) return fail(HFG_EINVAL, "host-only handle");
   if (B <= 0 || T <= 0) return fail(HFG_EINVAL, "B and T must be > 0");
+  if (B > kMaxBatch) return fail(HFG_EINVAL, "B must be in [1, 65535] (got %lld)", (long long)B);
   const size_t need = ws_bytes_for(h, B, T);
   if (need <= h->ws_bytes) return HFG_OK;
   DeviceGuard g(h->device);
@@ -306,6 +307,7 @@ int mrf_entry(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, f
   if (!x || !y || !ws) return fail(HFG_EINVAL, "x / y / workspace pointer is NULL");
   if (x == y) return fail(HFG_EINVAL, "y must not alias x");
   if (B <= 0 || L <= 0) return fail(HFG_EINVAL, "B and L must be > 0");
+  if (B > kMaxBatch) return fail(HFG_EINVAL, "B must be in [1, 65535] (got %lld)", (long long)B);
   if ((int64_t)h->stages[0].C * L >= ((int64_t)1 << 30))
     return fail(HFG_EINVAL, "per-item activation reaches 2^30 elements");
   ForwardScope scope(h);
@@ -318,7 +320,7 @@ int mrf_entry(hfg_handle* h, int only_j, const float* x, int64_t B, int64_t L, f
 }  // namespace
 
 size_t hfg_mrf_workspace_bytes(const hfg_handle* h, int64_t B, int64_t L) {
-  if (!h || !h->mrf_only || B <= 0 || L <= 0) return 0;
+  if (!h || !h->mrf_only || B <= 0 || B > kMaxBatch || L <= 0) return 0;
   return mrf_ws_layout(h, B, L).total;
 }
 

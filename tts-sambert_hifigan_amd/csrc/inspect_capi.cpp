@@ -266,6 +266,7 @@ int hfg_debug_workspace(const hfg_handle* h, int64_t B, int64_t T_or_L, int taps
                         size_t buflen) {
   if (!h || !buf || buflen == 0) return fail(HFG_EINVAL, "bad arguments");
   if (B <= 0 || T_or_L <= 0) return fail(HFG_EINVAL, "B and T (L) must be > 0");
+  if (B > kMaxBatch) return fail(HFG_EINVAL, "B must be in [1, 65535] (got %lld)", (long long)B);
   std::lock_guard<std::recursive_mutex> lk(const_cast<hfg_handle*>(h)->mu);
   const WsLayout lay = h->mrf_only ? mrf_ws_layout(h, B, T_or_L) : ws_layout(h, B, T_or_L, taps != 0);
   JsonWriter js;

@@ -48,6 +48,14 @@ def _lengths_on(lengths, device) -> torch.Tensor:
 
 
 PRECISIONS = ("f16x3", "fp32", "bf16x3", "bf16w")
+# the batch is a grid dimension of every kernel (include/hifigan_hip.h, "Batch limit")
+MAX_BATCH = 65535
+
+
+def _check_batch(B: int) -> None:
+    """Refuse a batch over the C ABI's limit before anything is allocated or moved."""
+    if B > MAX_BATCH:
+        raise RuntimeError(f"B must be in [1, {MAX_BATCH}], got {B}")
 
 
 def default_precision() -> str:
@@ -184,6 +192,7 @@ class _HipWeights(nn.Module):
         """y = MRF(x) (resblock < 0) or ResBlock_resblock(x) on the HIP device."""
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != channels:
             raise RuntimeError(f"expected x [B, {channels}, T], got {getattr(x, 'shape', type(x))}")
+        _check_batch(x.shape[0])
         if not x.is_cuda:
             raise RuntimeError("the MI355X ResBlock / MRF run on the HIP device only; move x to "
                                "'cuda' (there is no CPU fallback)")
@@ -407,6 +416,9 @@ class HiFiGANGenerator(_HipWeights):
         return self._handle_for(torch.device(device))
 
     def output_length(self, t: int) -> int:
+        """Samples of an item of ``t`` frames; an empty item (``t <= 0``) has none."""
+        if t <= 0:
+            return 0
         length = t
         for u, k in zip(self._hfg_cfg.up_rates[: self.num_upsamples],
                         self._hfg_cfg.up_kernels[: self.num_upsamples]):
@@ -436,6 +448,7 @@ class HiFiGANGenerator(_HipWeights):
         n_ch = mel.shape[1] if mel_layout == "bct" else mel.shape[2]
         if n_ch != self.n_mels:
             raise RuntimeError(f"expected {self.n_mels} mel channels, got {n_ch}")
+        _check_batch(mel.shape[0])
         if not mel.is_cuda:
             raise RuntimeError("HiFiGANGenerator (MI355X) runs on the HIP device only; "
                                "move the mel to 'cuda' (there is no CPU fallback)")
@@ -483,6 +496,8 @@ class HiFiGANGenerator(_HipWeights):
         reference's forward passes through (models/hifigan.py:238-251): "conv_pre",
         "ups.i" (after each ConvTranspose1d) and "mrfs.i" (after each MRF).  Inspection
         entry hfg_forward_taps (include/hifigan_hip_inspect.h); for parity checks."""
+        if isinstance(mel, torch.Tensor) and mel.dim() == 3:
+            _check_batch(mel.shape[0])
         if not (isinstance(mel, torch.Tensor) and mel.dim() == 3 and mel.is_cuda):
             raise RuntimeError("expected a HIP mel [B, n_mels, T]")
         B, _, T = mel.shape
