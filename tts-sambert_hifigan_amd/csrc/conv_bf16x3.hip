@@ -27,23 +27,13 @@
 #include "kernels.h"
 #include "launch.h"
 
-#ifndef HFG_AREG_AD
-#define HFG_AREG_AD 2
-#endif
-// tile-5 tap schedule: the next group's input loads issue at tap KT - HFG_AREG_XT; VALU
-// fillers per MFMA on the plain taps (HFG_AREG_NV) and on the last (store) tap
-// (HFG_AREG_NVST)
-#ifndef HFG_AREG_XT
-#define HFG_AREG_XT 4
-#endif
-#ifndef HFG_AREG_NV
-#define HFG_AREG_NV 2
-#endif
-#ifndef HFG_AREG_NVST
-#define HFG_AREG_NVST 6
-#endif
-
 namespace hfg {
+
+// tile-5 tap schedule: the next group's input loads issue at tap KT - kAregXt; VALU fillers
+// per MFMA on the plain taps (kAregNv) and on the last (store) tap (kAregNvSt)
+constexpr int kAregXt = 4;
+constexpr int kAregNv = 2;
+constexpr int kAregNvSt = 6;
 
 #if HFG_CONV_TIMING
 __device__ uint64_t g_cv_ts[kCvTs.words()];  // the clock stamps of this kernel (diag.h)
@@ -103,14 +93,12 @@ conv1d_bf16x3(const ConvParams p) {
   // block -> (column tile, m-tile, item).  Upsamplers: the m-tiles of one input window
   // (16 for ups.0) read the same x rows, so they are swizzled onto one XCD's L2 (blocks b
   // and b + 8 share an XCD under the round-robin placement; speed only, any placement is
-  // correct): linear id -> (id % 8) * (total / 8) + id / 8, then m-tile fastest.
+  // correct): xcd_swizzle of the linear id, then m-tile fastest.
   int tx = blockIdx.x, mt = blockIdx.y, b = blockIdx.z;
   if (UPS && p.ups_swz) {
     const int nx = gridDim.x, ny = gridDim.y;
     const int total = nx * ny * gridDim.z;
-    int id = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const int q = total >> 3;
-    if (id < (q << 3)) id = (id & 7) * q + (id >> 3);
+    int id = xcd_swizzle(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), total);
     mt = id % ny;
     id /= ny;
     tx = id % nx;
@@ -237,6 +225,9 @@ conv1d_bf16x3(const ConvParams p) {
       }
     }
   };
+  // bf16 offset of (window row t, 8-channel half h) in a staged plane: one 32-B row per t,
+  // the 16-B halves XOR-swizzled by bit 3 of t
+  auto xrow_off = [&](int t, int h) { return t * XROW + 8 * (h ^ ((t >> 3) & 1)); };
   auto store_x = [&](__bf16* Xh) {
     __bf16* Xl = Xh + xplane;
 #pragma unroll
@@ -268,18 +259,14 @@ conv1d_bf16x3(const ConvParams p) {
             }
             if constexpr (FMT == kFmtF16) a = a * sx;
           }
-          bf16x2_ hh, ll;
-          split2<FMT>(a, hh, ll);
-          h[e] = hh[0];
-          h[e + 1] = hh[1];
-          l[e] = ll[0];
-          l[e + 1] = ll[1];
+          split_into<FMT>(a[0], a[1], h, l, e);
         }
         const int t = i >> 1;
         // AREG: the two 8-channel halves in planes of their own (16-B rows: a half-wave's
         // 32 consecutive rows are one conflict-free 512-B run for any tap shift, so a tap
         // is one address add and the reads take immediate offsets); else one 32-B row per
-        // t with the 16-B halves XOR-swizzled
+        // t with the 16-B halves XOR-swizzled (xrow_off, written out: a call of the lambda
+        // here compiles to other code)
         const int off = AREG ? (i & 1) * HPS_AREG + t * 8
                              : t * XROW + 8 * ((i & 1) ^ ((t >> 3) & 1));
         *reinterpret_cast<bf16x8*>(Xh + off) = h;
@@ -299,20 +286,24 @@ conv1d_bf16x3(const ConvParams p) {
   struct Frag {
     bf16x8 ah[WM], al[WM], bh[WN], bl[WN];
   };
+  // the wave's A fragment i (plane pl: 0 hi, 1 lo) of tap jj of the chunk's slab
+  auto a_frag = [&](const __bf16* Ws, int jj, int i, int pl) {
+    return *reinterpret_cast<const bf16x8*>(Ws + jj * TAP_ELEMS + (wave_m * WM + i) * PK.row_tile +
+                                            lane * PK.lane + pl * PK.plane);
+  };
   // jj: tap inside the chunk's slab; tap: tap index inside the window
   auto load_frag = [&](const __bf16* Ws, const __bf16* Xh, int jj, int tap, Frag& f) {
     const __bf16* Xl = Xh + xplane;
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * PK.row_tile + lane * PK.lane;
-      f.ah[i] = *reinterpret_cast<const bf16x8*>(a);
-      f.al[i] = *reinterpret_cast<const bf16x8*>(a + PK.plane);
+      f.ah[i] = a_frag(Ws, jj, i, 0);
+      f.al[i] = a_frag(Ws, jj, i, 1);
     }
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
       const int t = wave_n * 32 * WN + k * 32 + col + tap * p.dil;
       // rows t..t+31 of one half-wave: (t mod 16) distinct -> conflict-free ds_read_b128
-      const int off = t * XROW + 8 * (half ^ ((t >> 3) & 1));
+      const int off = xrow_off(t, half);
       f.bh[k] = *reinterpret_cast<const bf16x8*>(Xh + off);
       f.bl[k] = *reinterpret_cast<const bf16x8*>(Xl + off);
     }
@@ -332,13 +323,12 @@ conv1d_bf16x3(const ConvParams p) {
     bf16x8 ah[WM], al[WM], bh[2], bl[2];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const __bf16* a = Ws + jj * TAP_ELEMS + (wave_m * WM + i) * PK.row_tile + lane * PK.lane;
-      ah[i] = *reinterpret_cast<const bf16x8*>(a);
-      al[i] = *reinterpret_cast<const bf16x8*>(a + PK.plane);
+      ah[i] = a_frag(Ws, jj, i, 0);
+      al[i] = a_frag(Ws, jj, i, 1);
     }
     auto ldb = [&](int k) {
       const int t = wave_n * 32 * WN + k * 32 + col + tap * p.dil;
-      const int off = t * XROW + 8 * (half ^ ((t >> 3) & 1));
+      const int off = xrow_off(t, half);
       bh[k & 1] = *reinterpret_cast<const bf16x8*>(Xh + off);
       bl[k & 1] = *reinterpret_cast<const bf16x8*>(Xl + off);
     };
@@ -350,20 +340,25 @@ conv1d_bf16x3(const ConvParams p) {
       for (int i = 0; i < WM; ++i) mma3<NP, FMT>(ah[i], al[i], bh[k & 1], bl[k & 1], acc[i][k]);
     }
   };
-  // sched_group_barrier pattern for tap_stream + staging work in one basic block: the A
-  // reads and the first B pair, then per MFMA up to NV VALU (+ one VMEM load when LD),
-  // the next B pair after each column tile's first MFMA, a DS write every 4th MFMA (ST)
-  auto pin_stream = [&](auto nv_tag, auto ld_tag, auto st_tag) {
+  // sched_group_barrier pattern for one tap (tap_stream, or the AREG path's tap_regs) +
+  // staging work in one basic block: the first LDS reads (tap_stream: the A reads and the
+  // first B pair; AREG: the first B pair unless the previous tap read it, pre_in), then per
+  // MFMA up to NV VALU (+ one VMEM load when LD), the next B pair after each column tile's
+  // first MFMA (AREG, after the last tile's: the next tap's first pair when pre_out), a DS
+  // write every 4th MFMA (ST)
+  auto pin_tap = [&](auto nv_tag, auto ld_tag, auto st_tag, bool pre_in = false,
+                     bool pre_out = false) {
     constexpr int NV = decltype(nv_tag)::value;
     constexpr bool LD = decltype(ld_tag)::value, ST = decltype(st_tag)::value;
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 * WM + 2, 0);
+    if constexpr (!AREG) __builtin_amdgcn_sched_group_barrier(0x100, 2 * WM + 2, 0);
+    else if (!pre_in) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
     for (int s = 0; s < NP * WM * WN; ++s) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
       if (LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       if (ST && s % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      if (s % (NP * WM) == 0 && s / (NP * WM) + 1 < WN)
+      if (s % (NP * WM) == 0 && (s / (NP * WM) + 1 < WN || pre_out))
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -409,7 +404,7 @@ conv1d_bf16x3(const ConvParams p) {
   cstamp(kCvTsPrologue);
 
   if constexpr (AREG) {
-    // ---- A fragments from global into registers, AD taps ahead; one barrier per
+    // ---- A fragments from global into registers, two taps ahead; one barrier per
     // channel group.  Every wave reads its own (wave_m) rows of the packed slab stream
     // (L2-resident; tile 3's packing) -- the two wave_n waves read the same rows -- so
     // the weights need no LDS and no cross-wave handoff.  The input window is
@@ -420,13 +415,12 @@ conv1d_bf16x3(const ConvParams p) {
     // hi*lo, hi*hi), so the result is bitwise the same.
     constexpr int KT = KT_;
     constexpr int NTG = (KT + TPC - 1) / TPC;
-    constexpr int AD = HFG_AREG_AD;           // A prefetch distance in taps (1 or 2)
-    constexpr int XT = KT >= HFG_AREG_XT ? KT - HFG_AREG_XT : 0;  // tap issuing the next
-                                                                  // group's input loads
-    static_assert(AD <= KT && XT < KT - 1, "AREG schedule");
+    constexpr int XT = KT >= kAregXt ? KT - kAregXt : 0;  // tap issuing the next group's
+                                                          // input loads
+    static_assert(2 <= KT && XT < KT - 1, "AREG schedule");
     using I0 = std::integral_constant<int, 0>;
-    using I2 = std::integral_constant<int, HFG_AREG_NV>;
-    using I6 = std::integral_constant<int, HFG_AREG_NVST>;
+    using I2 = std::integral_constant<int, kAregNv>;
+    using I6 = std::integral_constant<int, kAregNvSt>;
     using T_ = std::true_type;
     using F_ = std::false_type;
     const int NG = p.n_chunks / NTG;
@@ -438,7 +432,6 @@ conv1d_bf16x3(const ConvParams p) {
     const int a_lane = lane * (2 * PK.lane);
     typedef bf16x8 ASet[2][WM];
     ASet a0, a1, a2;
-    (void)a2;
     auto load_a = [&](ASet& d, int g, int t) {
       const int so = ((g * NTG + t / TPC) * SLAB + (t % TPC) * TAP_ELEMS + wm_u * WM * PK.row_tile) * 2;
 #pragma unroll
@@ -473,30 +466,11 @@ conv1d_bf16x3(const ConvParams p) {
           mma3<NP, FMT>(a[0][i], a[1][i], bh[k & 1], bl[k & 1], acc[i][k]);
       }
     };
-    // one tap's interleave: B(0) first (unless the previous tap read it), then per MFMA up to
-    // NV VALU and (LD) one global load, the next B pair after each column tile's first MFMA
-    // (after the last tile's: the next tap's first pair when pre_out), a DS write every 4th
-    // MFMA (ST)
-    auto pin_regs = [&](auto nv_tag, auto ld_tag, auto st_tag, bool pre_in, bool pre_out) {
-      constexpr int NV = decltype(nv_tag)::value;
-      constexpr bool LD = decltype(ld_tag)::value, ST = decltype(st_tag)::value;
-      if (!pre_in) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-#pragma unroll
-      for (int s = 0; s < NP * WM * WN; ++s) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
-        if (LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        if (ST && s % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        if (s % (NP * WM) == 0 && (s / (NP * WM) + 1 < WN || pre_out))
-          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
     load_a(a0, 0, 0);
-    if constexpr (AD == 2) load_a(a1, 0, 1);
+    load_a(a1, 0, 1);
     // raised for the whole channel-group loop, not per matrix phase as in the ResBlock and
     // upsampler kernels: this path has no separate staging phase to drop it for (load_x and
-    // store_x are interleaved into the taps' MFMA streams, pin_regs), so its staging loads,
+    // store_x are interleaved into the taps' MFMA streams, pin_tap), so its staging loads,
     // conversions and LDS writes run at priority 1 too; it drops for the epilogue
     prio_mfma();
     for (int g = 0; g < NG; ++g) {
@@ -505,30 +479,29 @@ conv1d_bf16x3(const ConvParams p) {
       const int gn = min(g + 1, NG - 1);
 #pragma unroll
       for (int t = 0; t < KT; ++t) {
-        // A of tap t + AD: the next group's first taps near the end (past the last group
+        // A of tap t + 2: the next group's first taps near the end (past the last group
         // a harmless re-read of its own)
-        ASet& an = AD == 2 ? a2 : a1;
-        if (t + AD < KT) load_a(an, g, t + AD);
-        else load_a(an, gn, t + AD - KT);
+        if (t + 2 < KT) load_a(a2, g, t + 2);
+        else load_a(a2, gn, t + 2 - KT);
         const bool pre_in = t > 0, pre_out = t + 1 < KT;
         if (t == XT) {
           load_x(gn);
           tap_regs(a0, Xh, t, pre_in, pre_out);
-          pin_regs(I0{}, T_{}, F_{}, pre_in, pre_out);
+          pin_tap(I0{}, T_{}, F_{}, pre_in, pre_out);
         } else if (t == KT - 1) {
           store_x(Xn);
           tap_regs(a0, Xh, t, pre_in, pre_out);
-          pin_regs(I6{}, T_{}, T_{}, pre_in, pre_out);
+          pin_tap(I6{}, T_{}, T_{}, pre_in, pre_out);
         } else {
           tap_regs(a0, Xh, t, pre_in, pre_out);
-          pin_regs(I2{}, T_{}, F_{}, pre_in, pre_out);
+          pin_tap(I2{}, T_{}, F_{}, pre_in, pre_out);
         }
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
           for (int i = 0; i < WM; ++i) {
             a0[pl][i] = a1[pl][i];
-            if constexpr (AD == 2) a1[pl][i] = a2[pl][i];
+            a1[pl][i] = a2[pl][i];
           }
       }
 #if HFG_CONV_TIMING
@@ -584,26 +557,26 @@ conv1d_bf16x3(const ConvParams p) {
           // also wait for the new slab
           store_x(Xn);
           tap_stream(Ws, Xh, 0, tap0);
-          pin_stream(I6{}, F_{}, T_{});
+          pin_tap(I6{}, F_{}, T_{});
           issue_next_w();
         } else if (ISX && !STX) {
           issue_next_w();
           __builtin_amdgcn_sched_barrier(0);  // the slab DMA stays older than the input loads
           load_x(gn);
           tap_stream(Ws, Xh, 0, tap0);
-          pin_stream(I3{}, T_{}, F_{});
+          pin_tap(I3{}, T_{}, F_{});
         } else {
           issue_next_w();
           if (ISX) load_x(gn);
           tap_stream(Ws, Xh, 0, tap0);
-          pin_stream(I0{}, F_{}, F_{});
+          pin_tap(I0{}, F_{}, F_{});
           if (STX) store_x(Xn);
         }
 #pragma unroll
         for (int jj = 1; jj < TPC; ++jj)
           if (jj < nt) {
             tap_stream(Ws, Xh, jj, tap0 + jj);
-            pin_stream(I0{}, F_{}, F_{});
+            pin_tap(I0{}, F_{}, F_{});
           }
         // the slab of chunk c+1 must have landed; younger: this chunk's input loads
         if (ISX && !STX) wait_x(std::integral_constant<int, NX>{});
@@ -693,9 +666,7 @@ conv1d_bf16x3(const ConvParams p) {
     const int sh = __builtin_ctz((unsigned)s_);
     auto co_of = [&](int row) { return pow2 ? row >> sh : row / s_; };
     float vmax = 0.f;  // max |stored value| (f16x3 consumers: p.amax_out)
-    auto track4 = [&](const float4& v) {
-      vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    };
+    auto track4 = [&](const float4& v) { vmax = fmaxf(vmax, absmax4(v)); };
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
       const int rb = mt * MT + wave_m * 32 * WM + i * 32 + 4 * half;  // row of r = 0

@@ -499,9 +499,7 @@ hipError_t launch_stage_lengths(const int32_t* lens, int B, const StageLenParams
 // grid is capped near two blocks per CU and each block folds its max into one atomic: a grid
 // that finishes all at once queues its scale atomics on the item's slot lines (kernels.h;
 // round 6: 48 us for 8192 waves on the 2-line slots at C1).
-#ifndef HFG_COMBINE_BLOCKS
-#define HFG_COMBINE_BLOCKS 512
-#endif
+constexpr int kCombineBlocks = 512;
 template <int NMAX>
 __device__ __forceinline__ void mrf_combine_body(const MrfCombineArgs& a, int b, float& vmax) {
   const int len_b = a.len ? min(a.len[b], a.L) : a.L;
@@ -525,18 +523,10 @@ __device__ __forceinline__ void mrf_combine_body(const MrfCombineArgs& a, int b,
       float4 acc = v[0];
 #pragma unroll
       for (int j = 1; j < NMAX; ++j)
-        if (j < a.n) {
-          acc.x = acc.x + v[j].x;
-          acc.y = acc.y + v[j].y;
-          acc.z = acc.z + v[j].z;
-          acc.w = acc.w + v[j].w;
-        }
-      acc.x = acc.x / a.div;
-      acc.y = acc.y / a.div;
-      acc.z = acc.z / a.div;
-      acc.w = acc.w / a.div;
+        if (j < a.n) acc = add4(acc, v[j]);
+      acc = div4(acc, a.div);
       *reinterpret_cast<float4*>(y + i) = acc;
-      vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(acc.x), fabsf(acc.y)), fmaxf(fabsf(acc.z), fabsf(acc.w))));
+      vmax = fmaxf(vmax, absmax4(acc));
     } else {
       // a group of 4 can straddle two channel rows: each sample tests its own column
       // (skipping the group on its first sample's column lost the next row's first
@@ -574,7 +564,7 @@ hipError_t launch_mrf_combine(const MrfCombineArgs& a, int batch, hipStream_t st
   const int64_t n4 = ((int64_t)a.C * a.L + 3) / 4;
   // about two blocks per CU over the whole batch (the launch is HBM-bound: 256 CUs x 2 x 256
   // threads keep enough float4 loads in flight), at least one block per item
-  const int64_t cap = std::max<int64_t>(1, HFG_COMBINE_BLOCKS / batch);
+  const int64_t cap = std::max<int64_t>(1, kCombineBlocks / batch);
   const int gx = (int)std::min<int64_t>((n4 + 255) / 256, cap);
   mrf_combine_kernel<<<dim3(gx, batch), dim3(256), 0, stream>>>(a);
   return hipGetLastError();

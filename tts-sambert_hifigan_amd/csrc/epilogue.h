@@ -73,6 +73,39 @@ __device__ __forceinline__ void amax_commit(float m, uint32_t* slots, int b) {
   if ((threadIdx.x & 63) == 0) atomicMax(slot, __builtin_bit_cast(uint32_t, m));
 }
 
+// ---- float4 output arithmetic, per component, in the order the scalar epilogue applies it ----
+// (the arithmetic takes references and the store a value: the other way round either moves
+// mrf_combine_kernel's or conv1d_mfma_f32's code; conv_epilogue_lds2 keeps its written-out
+// text, through these it compiles to other code on all its instances: DESIGN.md "Kernel units")
+// fma(v, sc, bv): the accumulator's unscale joined with the bias add
+__device__ __forceinline__ float4 fma4(float a, float b, float c, float d, float sc, float bv) {
+  return float4{__builtin_fmaf(a, sc, bv), __builtin_fmaf(b, sc, bv), __builtin_fmaf(c, sc, bv),
+                __builtin_fmaf(d, sc, bv)};
+}
+__device__ __forceinline__ float4 fma4(const float4& v, float sc, float bv) {
+  return fma4(v.x, v.y, v.z, v.w, sc, bv);
+}
+__device__ __forceinline__ float4 add4(const float4& a, const float4& b) {
+  return float4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
+}
+// leaky_relu as the reference's select
+__device__ __forceinline__ float4 lrelu4(const float4& v) {
+  return float4{v.x > 0.f ? v.x : v.x * kLReluSlope, v.y > 0.f ? v.y : v.y * kLReluSlope,
+                v.z > 0.f ? v.z : v.z * kLReluSlope, v.w > 0.f ? v.w : v.w * kLReluSlope};
+}
+__device__ __forceinline__ float4 div4(const float4& v, float d) {
+  return float4{v.x / d, v.y / d, v.z / d, v.w / d};
+}
+__device__ __forceinline__ float absmax4(const float4& v) {
+  return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+}
+// streamed once (the next launch reads it from HBM / MALL): non-temporal
+__device__ __forceinline__ void store4_nt(float* dst, float4 v) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v nv = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(nv, reinterpret_cast<f4v*>(dst));
+}
+
 // sc: the accumulator's scale (f16x3: 2^-(e_x + e_w); 1 otherwise): v = fma(acc, sc, bias),
 // bitwise acc + bias for sc = 1
 template <int WM, int WN>
@@ -228,57 +261,30 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, floatx16e
         geom(it0 + u, row[u], n[u], ok[u]);
         full[u] = ok[u] && n[u] + 3 < N_b;
         v[u] = *reinterpret_cast<const float4*>(stage + rr * SROW + 4 * c4);
-        const float bv = p.bias[row[u]];
-        v[u].x = __builtin_fmaf(v[u].x, sc, bv);
-        v[u].y = __builtin_fmaf(v[u].y, sc, bv);
-        v[u].z = __builtin_fmaf(v[u].z, sc, bv);
-        v[u].w = __builtin_fmaf(v[u].w, sc, bv);
+        v[u] = fma4(v[u], sc, p.bias[row[u]]);
       }
       if (resb) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float4 rv = rvb[cur][u];
-          v[u].x = rv.x + v[u].x;
-          v[u].y = rv.y + v[u].y;
-          v[u].z = rv.z + v[u].z;
-          v[u].w = rv.w + v[u].w;
-        }
+        for (int u = 0; u < 4; ++u) v[u] = add4(rvb[cur][u], v[u]);
       }
       if (act) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          v[u].x = v[u].x > 0.f ? v[u].x : v[u].x * kLReluSlope;
-          v[u].y = v[u].y > 0.f ? v[u].y : v[u].y * kLReluSlope;
-          v[u].z = v[u].z > 0.f ? v[u].z : v[u].z * kLReluSlope;
-          v[u].w = v[u].w > 0.f ? v[u].w : v[u].w * kLReluSlope;
-        }
+        for (int u = 0; u < 4; ++u) v[u] = lrelu4(v[u]);
       }
       if (add_mrf) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float4 mv = mvb[cur][u];
-          v[u].x = mv.x + v[u].x;
-          v[u].y = mv.y + v[u].y;
-          v[u].z = mv.z + v[u].z;
-          v[u].w = mv.w + v[u].w;
-        }
+        for (int u = 0; u < 4; ++u) v[u] = add4(mvb[cur][u], v[u]);
       }
       if (div_mrf) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          v[u].x = v[u].x / p.mrf_div;
-          v[u].y = v[u].y / p.mrf_div;
-          v[u].z = v[u].z / p.mrf_div;
-          v[u].w = v[u].w / p.mrf_div;
-        }
+        for (int u = 0; u < 4; ++u) v[u] = div4(v[u], p.mrf_div);
       }
       if (p.amax_out) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           // the stored elements only: a partial quad's tail past N_b is not written
           if (full[u]) {
-            vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)),
-                                     fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+            vmax = fmaxf(vmax, absmax4(v[u]));
           } else if (ok[u]) {
             const int nv = N_b - n[u];
             vmax = fmaxf(vmax, fabsf(v[u].x));
@@ -291,10 +297,7 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, floatx16e
       for (int u = 0; u < 4; ++u) {
         float* dst = outb + (int64_t)row[u] * p.N + n[u];
         if (full[u]) {
-          // streamed once (the next launch reads it from HBM / MALL): non-temporal
-          typedef float f4v __attribute__((ext_vector_type(4)));
-          const f4v nv = {v[u].x, v[u].y, v[u].z, v[u].w};
-          __builtin_nontemporal_store(nv, reinterpret_cast<f4v*>(dst));
+          store4_nt(dst, v[u]);
         } else if (ok[u]) {
           dst[0] = v[u].x;
           if (n[u] + 1 < N_b) dst[1] = v[u].y;

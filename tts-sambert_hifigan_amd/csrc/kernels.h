@@ -312,12 +312,8 @@ hipError_t launch_mrf_thin(int C, const ThinParams& p, int batch, hipStream_t st
 // the same MRF on the 16x16x32 matrix cores in split precision (bf16x3 / f16x3 products):
 // 4 waves x kThinMfmaTiles 16-column tiles (a 512-column window), C = 16
 constexpr int kThinMfmaTiles = 8;
-// operand buffers of mrf_thin_mfma: 2 = one barrier per conv (conv1 / conv2 alternate),
-// 1 = rewritten in place (two barriers per conv; round 2)
-#ifndef HFG_THIN_BUFS
-#define HFG_THIN_BUFS 2
-#endif
-constexpr int kThinMfmaBufs = HFG_THIN_BUFS;
+// operand buffers of mrf_thin_mfma: conv1 and conv2 alternate, one barrier per conv
+constexpr int kThinMfmaBufs = 2;
 constexpr int kThinMfmaMaxSteps = 4;  // k-steps per conv (k <= 7 at C = 16)
 int thin_mfma_window(int C);  // 0: unsupported C
 size_t thin_mfma_lds_bytes(int C);

@@ -106,17 +106,9 @@ mrf_thin_mfma(const ThinParams p) {
     for (int t = 0; t < NCT; ++t) {
       bf16x4 h, l;
 #pragma unroll
-      for (int i = 0; i < 4; i += 2) {
-        floatx2_ a;
-        a[0] = vk[t] ? fmaxf(v[t][i] * sc, v[t][i] * sc1) : 0.f;
-        a[1] = vk[t] ? fmaxf(v[t][i + 1] * sc, v[t][i + 1] * sc1) : 0.f;
-        bf16x2_ hh, ll;
-        split2<FMT>(a, hh, ll);
-        h[i] = hh[0];
-        h[i + 1] = hh[1];
-        l[i] = ll[0];
-        l[i + 1] = ll[1];
-      }
+      for (int i = 0; i < 4; i += 2)
+        split_into<FMT>(vk[t] ? fmaxf(v[t][i] * sc, v[t][i] * sc1) : 0.f,
+                        vk[t] ? fmaxf(v[t][i + 1] * sc, v[t][i + 1] * sc1) : 0.f, h, l, i);
       const int off = opnd_off(cbase + 16 * t + MARG, chan(0));
       *reinterpret_cast<bf16x4*>(buf + off) = h;
       *reinterpret_cast<bf16x4*>(buf + PS + off) = l;
@@ -223,17 +215,14 @@ mrf_thin_mfma(const ThinParams p) {
     for (int cv = cv0; cv < cv1; cv += 2) {
       // two operand buffers (kThinMfmaBufs = 2): conv1 reads buffer 0, conv2 buffer 1, so a
       // buffer is rewritten only after the barrier that follows every read of it (one
-      // barrier per conv; f16x3 adds the one of block_exp); one buffer: rewritten in place
-      // between two barriers
+      // barrier per conv; f16x3 adds the one of block_exp)
       char* const b0 = lds;
-      char* const b1 = lds + (kThinMfmaBufs - 1) * 2 * PS;
+      char* const b1 = lds + 2 * PS;
       int ex = 0;
-      if (kThinMfmaBufs == 1 && FMT != kFmtF16) __syncthreads();
       if constexpr (FMT == kFmtF16) ex = block_exp(xr, radius);
       write_operand(xr, b0, exp2i(ex));
       __syncthreads();
       run_conv(cv, b0, sa0, sa1, sb0, sb1, exp2i(-(ex + p.ew[cv])));
-      if (kThinMfmaBufs == 1 && FMT != kFmtF16) __syncthreads();
       radius += (p.kt[cv] - 1) / 2 * p.dil[cv];
       if constexpr (FMT == kFmtF16) ex = block_exp(acc, radius);
       write_operand(acc, b1, exp2i(ex));

@@ -291,17 +291,9 @@ resblock_bf16x3(const RbParams p) {
         const int off = gq * GS + hh * HPS + (c + MARG) * 16;
         bf16x8 h, l;
 #pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          floatx2_ a;
-          a[0] = fmaxf(mg[q][e] * sc, mg[q][e] * (kLReluSlope * sc));
-          a[1] = fmaxf(mg[q][e + 1] * sc, mg[q][e + 1] * (kLReluSlope * sc));
-          bf16x2_ hh2, ll;
-          split2<FMT>(a, hh2, ll);
-          h[e] = hh2[0];
-          h[e + 1] = hh2[1];
-          l[e] = ll[0];
-          l[e + 1] = ll[1];
-        }
+        for (int e = 0; e < 8; e += 2)
+          split_into<FMT>(fmaxf(mg[q][e] * sc, mg[q][e] * (kLReluSlope * sc)),
+                          fmaxf(mg[q][e + 1] * sc, mg[q][e + 1] * (kLReluSlope * sc)), h, l, e);
         *reinterpret_cast<bf16x8*>(lds + off) = h;
         *reinterpret_cast<bf16x8*>(lds + off + PS) = l;
       }
@@ -335,16 +327,8 @@ resblock_bf16x3(const RbParams p) {
           bf16x8 h, l;
 #pragma unroll
           for (int e = 0; e < 8; e += 2) {
-            floatx2_ a;
             const float v0 = v[i][k][gg * 8 + e], v1 = v[i][k][gg * 8 + e + 1];
-            a[0] = fmaxf(v0 * f1, v0 * f2);
-            a[1] = fmaxf(v1 * f1, v1 * f2);
-            bf16x2_ hh, ll;
-            split2<FMT>(a, hh, ll);
-            h[e] = hh[0];
-            h[e + 1] = hh[1];
-            l[e] = ll[0];
-            l[e + 1] = ll[1];
+            split_into<FMT>(fmaxf(v0 * f1, v0 * f2), fmaxf(v1 * f1, v1 * f2), h, l, e);
           }
           char* dst = lds + (row0 / 16 + 2 * i + gg) * GS + vb + k * 512;
           *reinterpret_cast<bf16x8*>(dst) = h;

@@ -39,21 +39,12 @@
 #include "kernels.h"
 #include "launch.h"
 
-// u = 2 epilogue: 16-B stores through a DPP pair swap (1) or 8-B stores (0)
-#ifndef HFG_UPS_PAIR
-#define HFG_UPS_PAIR 1
-#endif
-
-#ifndef HFG_UPS_SMALL_OCC
-#define HFG_UPS_SMALL_OCC 3
-#endif
-
 namespace hfg {
 
 // occupancy: the small tile (2 x 32 x 32 accumulators per class) fits 168 VGPRs, 3 waves per
 // SIMD; its launches (the thin last upsampler) are bound by HBM latency, not the matrix pipe
 template <int WAVES_M, int WAVES_N, int WM, int WN>
-constexpr int ups_min_blocks() { return WAVES_M * WM * WN <= 2 ? HFG_UPS_SMALL_OCC : 2; }
+constexpr int ups_min_blocks() { return WAVES_M * WM * WN <= 2 ? 3 : 2; }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int NP, int FMT>
 __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, (ups_min_blocks<WAVES_M, WAVES_N, WM, WN>()))
@@ -103,10 +94,7 @@ ups_bf16x3(const UpsParams p) {
   // window run on one XCD (blocks b and b + 8 share an XCD under round-robin placement)
   int mt, tx, b;
   {
-    const int total = p.m_tiles * p.n_tiles * p.batch;
-    int id = blockIdx.x;
-    const int q = total >> 3;
-    if (id < (q << 3)) id = (id & 7) * q + (id >> 3);
+    int id = xcd_swizzle(blockIdx.x, p.m_tiles * p.n_tiles * p.batch);
     mt = id % p.m_tiles;
     id /= p.m_tiles;
     tx = id % p.n_tiles;
@@ -191,17 +179,9 @@ ups_bf16x3(const UpsParams p) {
     for (int j = 0; j < 4; ++j) {
       bf16x4_ hv, lv;
 #pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        floatx2_ a;
-        a[0] = okt[j] ? fmaxf(xv[e][j] * sx, xv[e][j] * sx1) : 0.f;
-        a[1] = okt[j] ? fmaxf(xv[e + 1][j] * sx, xv[e + 1][j] * sx1) : 0.f;
-        bf16x2_ hh, ll;
-        split2<FMT>(a, hh, ll);
-        hv[e] = hh[0];
-        hv[e + 1] = hh[1];
-        lv[e] = ll[0];
-        lv[e + 1] = ll[1];
-      }
+      for (int e = 0; e < 4; e += 2)
+        split_into<FMT>(okt[j] ? fmaxf(xv[e][j] * sx, xv[e][j] * sx1) : 0.f,
+                        okt[j] ? fmaxf(xv[e + 1][j] * sx, xv[e + 1][j] * sx1) : 0.f, hv, lv, e);
       const int off = xrow_off(4 * xq + j, hf) + 8 * (cq & 1);
       *reinterpret_cast<bf16x4_*>(xh + off) = hv;
       *reinterpret_cast<bf16x4_*>(xh + XPLANE + off) = lv;
@@ -315,7 +295,7 @@ ups_bf16x3(const UpsParams p) {
     for (int k = 0; k < WN; ++k) {
       const int m = m0 + wave_n * 32 * WN + k * 32 + col;
       if (m >= T_b) continue;
-      if (h == 1 && HFG_UPS_PAIR) {
+      if (h == 1) {
         // rows = channels: (L, R) = samples 2m, 2m + 1.  Adjacent lanes (frames m, m + 1,
         // m even) swap one channel's pair (DPP quad_perm [1,0,3,2]): the even lane then
         // holds samples 2m .. 2m + 3 of channel r, the odd lane those of channel r + 1 ->
@@ -359,18 +339,6 @@ ups_bf16x3(const UpsParams p) {
             t2(l1, r1);
           }
         }
-      } else if (h == 1) {
-        // rows = channels: (L, R) = samples 2m, 2m + 1
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int co = rb + acc_row(r);
-          const float bv = bvr[r];
-          floatx2_ v;
-          v[0] = __builtin_fmaf(acc[0][i][k][r], sc, bv);
-          v[1] = __builtin_fmaf(acc[1][i][k][r], sc, bv);
-          if (!(kAblate && (p.dbg & kAblUpsNoStoreY))) *reinterpret_cast<floatx2_*>(yb + (int64_t)co * p.L_out + 2 * m) = v;
-          t2(v[0], v[1]);
-        }
       } else if (h == 2) {
         // rows (co, 0), (co, 1), (co + 1, 0), (co + 1, 1): samples 4m .. 4m + 3 of co, co + 1
 #pragma unroll
@@ -380,11 +348,8 @@ ups_bf16x3(const UpsParams p) {
             const int r0 = 4 * q + 2 * pr;
             const int co = (rb + 8 * q + 2 * pr) >> 1;
             const float bv = bvr[2 * q + pr];
-            float4 v;
-            v.x = __builtin_fmaf(acc[0][i][k][r0], sc, bv);
-            v.y = __builtin_fmaf(acc[0][i][k][r0 + 1], sc, bv);
-            v.z = __builtin_fmaf(acc[1][i][k][r0], sc, bv);
-            v.w = __builtin_fmaf(acc[1][i][k][r0 + 1], sc, bv);
+            const float4 v = fma4(acc[0][i][k][r0], acc[0][i][k][r0 + 1], acc[1][i][k][r0],
+                                  acc[1][i][k][r0 + 1], sc, bv);
             if (!(kAblate && (p.dbg & kAblUpsNoStoreY))) *reinterpret_cast<float4*>(yb + (int64_t)co * p.L_out + 4 * m) = v;
             t2(v.x, v.y);
             t2(v.z, v.w);
@@ -398,11 +363,8 @@ ups_bf16x3(const UpsParams p) {
           const float bv = bvr[q];
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
-            float4 v;
-            v.x = __builtin_fmaf(acc[c][i][k][4 * q + 0], sc, bv);
-            v.y = __builtin_fmaf(acc[c][i][k][4 * q + 1], sc, bv);
-            v.z = __builtin_fmaf(acc[c][i][k][4 * q + 2], sc, bv);
-            v.w = __builtin_fmaf(acc[c][i][k][4 * q + 3], sc, bv);
+            const float4 v = fma4(acc[c][i][k][4 * q + 0], acc[c][i][k][4 * q + 1],
+                                  acc[c][i][k][4 * q + 2], acc[c][i][k][4 * q + 3], sc, bv);
             if (!(kAblate && (p.dbg & kAblUpsNoStoreY))) *reinterpret_cast<float4*>(yb + (int64_t)co * p.L_out + m * p.u + c * h + sp) = v;
             t2(v.x, v.y);
             t2(v.z, v.w);
