@@ -340,4 +340,12 @@ int hfg_resample_forward(hfg_resample_handle* h, const float* x, int64_t B, int6
  * ------------------------------------------------------------------------- */
 #include "hifigan_hip_specdist.h"
 
+/* ---------------------------------------------------------------------------
+ * The reference's discriminators (ScaleDiscriminator, PeriodDiscriminator) as
+ * forward-only networks, every feature map written in the reference's layout,
+ * and the deterministic feature-matching sums: the hfg_disc section, in a header
+ * of its own.
+ * ------------------------------------------------------------------------- */
+#include "hifigan_hip_disc.h"
+
 #endif /* HIFIGAN_HIP_H */

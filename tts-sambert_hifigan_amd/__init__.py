@@ -12,6 +12,7 @@ from ._lib import (HipExtensionMissing, HfgError, Handle, load_library, make_con
                    schedule_overrides)
 from . import pcm  # noqa: F401  (the release's PCM boundary: pcm.peak / to_float / to_pcm16)
 from . import metrics  # noqa: F401  (spectral distances: metrics.mel_distance / MultiResolutionSTFT)
+from . import discriminators  # noqa: F401  (the reference's MSD / MPD, forward only)
 
 __all__ = ["HiFiGAN", "HiFiGANGenerator", "MRF", "ResBlock", "ResBlock2", "get_padding", "Handle",
            "HipExtensionMissing", "HfgError", "load_library", "make_config", "LIB_PATH", "check_provenance",

@@ -292,6 +292,26 @@ SPECDIST_SIGNATURES = {
 }
 
 
+DISC_KINDS = {"period": 0, "scale": 1}   # HFG_DISC_PERIOD / HFG_DISC_SCALE
+
+# every symbol declared in include/hifigan_hip_disc.h (the discriminators)
+DISC_SIGNATURES = {
+    "hfg_disc_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "hfg_disc_destroy": (None, [c_void_p]),
+    "hfg_disc_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
+    "hfg_disc_commit": (c_int, [c_void_p]),
+    "hfg_disc_num_maps": (c_int, [c_void_p]),
+    "hfg_disc_map_shape": (c_int, [c_void_p, c_int64, c_int, POINTER(c_int64)]),
+    "hfg_disc_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
+    "hfg_disc_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(c_void_p),
+                                 c_void_p, c_size_t, c_void_p]),
+    "hfg_disc_fm_workspace_bytes": (c_size_t, [c_void_p, c_int64]),
+    "hfg_disc_fm_sums": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_void_p),
+                                 POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hfg_disc_debug_unpacked": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), c_size_t]),
+}
+
+
 def load_library(path: str = LIB_PATH):
     """Open libhifigan_hip.so (cached).  Raises HipExtensionMissing if absent."""
     global _lib
@@ -307,7 +327,8 @@ def load_library(path: str = LIB_PATH):
     allow_old = os.environ.get("HFG_ALLOW_OLD_LIB") == "1"
     missing = []
     for name, (res, args) in {**SIGNATURES, **RELMEL_SIGNATURES, **PCM_SIGNATURES,
-                              **RESAMPLE_EX_SIGNATURES, **SPECDIST_SIGNATURES}.items():
+                              **RESAMPLE_EX_SIGNATURES, **SPECDIST_SIGNATURES,
+                              **DISC_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             missing.append(name)

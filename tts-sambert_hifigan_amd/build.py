@@ -18,7 +18,8 @@ SOURCES = ["conv_kernels.hip", "conv_bf16x3.hip", "resblock_bf16x3.hip",
            "mrf_thin.hip", "mrf_thin_mfma.hip", "ups_bf16x3.hip", "probe.hip", "hifigan_capi.cpp",
            "plan.cpp", "pack.cpp", "forward.cpp", "inspect_capi.cpp", "mel_kernels.hip",
            "resample.hip", "pcm.hip", "spectral_distance.hip", "mel_capi.cpp", "relmel_capi.cpp",
-           "resample_capi.cpp", "pcm_capi.cpp", "specdist_capi.cpp"]
+           "resample_capi.cpp", "pcm_capi.cpp", "specdist_capi.cpp", "disc_conv.hip",
+           "disc_thin.hip", "disc_capi.cpp"]
 
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -148,3 +148,25 @@ def load_generator_checkpoint(gen, src: Union[str, Mapping], strict: bool = True
     wn = any(k.endswith(".weight_g") for k in target.state_dict())
     sd = convert_state_dict(obj, target.num_kernels, target.num_upsamples, weight_normed=wn)
     return target.load_state_dict(sd, strict=strict)
+
+
+def load_discriminator_checkpoint(src: Union[str, Mapping], map_location: Optional[str] = "cpu"
+                                  ) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+    """``(msd_state, mpd_state)`` of a training checkpoint of the reference ``HiFiGAN`` wrapper
+    (models/hifigan.py:618-800), the counterpart of ``load_generator_checkpoint``: a file
+    (``torch.load(..., weights_only=True)``) or mapping, through the same containers
+    (``"model"``, ``"state_dict"``, ...) and DistributedDataParallel ``module.`` prefixes; the
+    keys under ``msd.`` and ``mpd.`` with the prefix taken off, ready for
+    ``MultiScaleDiscriminator.load_state_dict`` / ``MultiPeriodDiscriminator.load_state_dict``
+    (``strict=True``).  Weight norm is kept (the modules carry it)."""
+    obj = torch.load(src, map_location=map_location, weights_only=True) if isinstance(src, str) \
+        else src
+    strip = re.compile(r"^(module\.)+")
+    sd = {strip.sub("", k): v for k, v in _unwrap(obj).items()}
+    out = []
+    for prefix in ("msd.", "mpd."):
+        part = {strip.sub("", k[len(prefix):]): v for k, v in sd.items() if k.startswith(prefix)}
+        if not part:
+            raise ValueError(f"the checkpoint holds no '{prefix}*' keys")
+        out.append(part)
+    return out[0], out[1]

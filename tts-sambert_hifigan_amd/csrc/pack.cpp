@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "disc.h"
 #include "handle.h"
 
 using hfg::kTiles;
@@ -239,6 +240,37 @@ int pack_weights(hfg_handle* h) {
     if (st.thin) pack_thin(h, st);
   }
   return HFG_OK;
+}
+
+// disc_conv (disc.h): the groups one after another, each through disc_conv_nest; f16x3 with
+// the layer's exponent
+int pack_disc_conv(const float* w, int cig, int cog, int k, int groups, int msub, uint16_t* dst) {
+  const PackNest n = hfg::disc_conv_nest(cig, cog, k, msub);
+  const size_t per = hfg::disc_conv_group_elems(cig, cog, k, msub);
+  float m = 0.f;
+  for (size_t i = 0; i < (size_t)groups * cog * cig * k; ++i) m = std::max(m, std::fabs(w[i]));
+  const int ew = x3_exp_host(m);
+  const WSplit ws{hfg::kFmtF16, std::ldexp(1.0f, ew)};
+  for (int g = 0; g < groups; ++g) {
+    const float* wg = w + (size_t)g * cog * cig * k;
+    fill_split(n, dst + g * per, &ws, [&](const PackAt& a) {
+      return a.tap < k ? wg[((size_t)a.row * cig + a.ci) * k + a.tap] : 0.f;
+    });
+  }
+  return ew;
+}
+
+void unpack_disc_conv(const uint16_t* src, int cig, int cog, int k, int groups, int msub,
+                      int plane, int ew, float* w) {
+  const PackNest n = hfg::disc_conv_nest(cig, cog, k, msub);
+  const size_t per = hfg::disc_conv_group_elems(cig, cog, k, msub);
+  for (int g = 0; g < groups; ++g) {
+    float* wg = w + (size_t)g * cog * cig * k;
+    for_each_packed(n, [&](size_t i, const PackAt& a) {
+      if (a.tap < k && a.plane == plane)
+        wg[((size_t)a.row * cig + a.ci) * k + a.tap] = std::ldexp(h2f(src[g * per + i]), -ew);
+    });
+  }
 }
 
 }  // namespace hfg_host

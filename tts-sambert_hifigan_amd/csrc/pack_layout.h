@@ -250,6 +250,57 @@ constexpr PackNest conv_post_nest(int C) {
   return n.dim(C, kConvPostTaps, {0, 1, 0, 0, 0}).dim(kConvPostTaps, 1, {0, 0, 1, 0, 0});
 }
 
+// ---- disc_conv (disc_conv.hip): the discriminators' grouped, strided convs; 16-bit halves
+// (f16x3: f16 hi and lo planes of the weights scaled by the layer's power of two) ----
+// per group [m_tile][chunk][step][msub][plane][lane][8], the groups one after another: row
+// (within the group) = 16 MSUB m_tile + 16 msub + (lane & 15); a k-step is four octets of
+// 8 channels at one tap, octet o = 4 step + (lane >> 4): tap = o / O (zero past k),
+// ci (within the group) = CK chunk + 8 (o % O) + e with CK = min(C_in / groups, 32) channels
+// per chunk and O = CK / 8 octets per tap.
+constexpr int kDiscCkMax = 32;
+struct DiscConvPack {
+  int lane;   // a lane's 8 channels (16 B)
+  int plane;  // 64 lanes: 16 rows x 4 octets
+  int msub;   // hi + lo: one 16-row tile of one k-step
+  int step;   // MSUB row tiles
+};
+constexpr DiscConvPack disc_conv_pack(int MSUB) {
+  DiscConvPack l{};
+  l.lane = 8;
+  l.plane = 64 * l.lane;
+  l.msub = 2 * l.plane;
+  l.step = MSUB * l.msub;
+  return l;
+}
+__host__ __device__ constexpr int disc_conv_ck(int cig) { return cig < kDiscCkMax ? cig : kDiscCkMax; }
+// group widths the layout holds: 8, 16 or a multiple of 32 input channels, whole 16-row tiles
+constexpr bool disc_conv_widths_ok(int cig, int cog, int MSUB) {
+  return (cig == 8 || cig == 16 || (cig > 0 && cig % 32 == 0)) && cog > 0 && cog % (16 * MSUB) == 0;
+}
+__host__ __device__ constexpr int disc_conv_steps(int cig, int k) {
+  return (k * (disc_conv_ck(cig) / 8) + 3) / 4;
+}
+// 16-bit elements of one group's packing, and floats of a whole layer's
+constexpr size_t disc_conv_group_elems(int cig, int cog, int k, int MSUB) {
+  return (size_t)(cog / (16 * MSUB)) * (cig / disc_conv_ck(cig)) * disc_conv_steps(cig, k) *
+         disc_conv_pack(MSUB).step;
+}
+constexpr size_t disc_conv_pack_floats(int cig, int cog, int k, int groups, int MSUB) {
+  return pack_floats_of_bf16((size_t)groups * disc_conv_group_elems(cig, cog, k, MSUB));
+}
+constexpr PackNest disc_conv_nest(int cig, int cog, int k, int MSUB) {
+  const DiscConvPack l = disc_conv_pack(MSUB);
+  const int CK = disc_conv_ck(cig), O = CK / 8, steps = disc_conv_steps(cig, k);
+  const int chunks = cig / CK;
+  PackNest n;
+  n.dim(cog / (16 * MSUB), (size_t)chunks * steps * l.step, {16 * MSUB, 0, 0, 0, 0});
+  n.dim(chunks, (size_t)steps * l.step, {0, CK, 0, 0, 0});
+  n.dim(steps, l.step, {0, 0, 4 / O, 0, 0}).dim(MSUB, l.msub, {16, 0, 0, 0, 0});
+  n.dim(2, l.plane, {0, 0, 0, 1, 0});
+  n.dim(4 / O, (size_t)O * 16 * l.lane, {0, 0, 1, 0, 0}).dim(O, 16 * l.lane, {0, 8, 0, 0, 0});
+  return n.dim(16, l.lane, {1, 0, 0, 0, 0}).dim(8, 1, {0, 1, 0, 0, 0});
+}
+
 // ---- self-check: every nest is dense (last index + 1 = extents' product = the size) ----
 constexpr bool pack_dense(const PackNest& n, size_t elems) {
   return n.last() + 1 == elems && n.count() == elems;
@@ -272,6 +323,11 @@ constexpr bool pack_layouts_dense() {
   for (int k : {3, 5, 7})
     ok = ok && pack_dense(thin_mfma_nest(16, k), thin_mfma_conv_bytes(16, k) / 2) &&
          pack_dense(thin_nest(8, k), thin_pack_floats(8, k));
+  for (int cig : {8, 16, 32, 64})
+    for (int k : {5, 41})
+      for (int MSUB : {1, 2, 4})
+        ok = ok && pack_dense(disc_conv_nest(cig, 64, k, MSUB),
+                              disc_conv_group_elems(cig, 64, k, MSUB));
   return ok && pack_dense(conv_post_nest(32), conv_post_pack_floats(32));
 }
 static_assert(pack_layouts_dense(), "a packed-operand nest is not dense");

@@ -115,6 +115,25 @@ def copy_synthesis_error(gen, frontend, wav: torch.Tensor, lengths=None):
     return out, metrics.mel_distance(frontend, out, mel, frame_lengths * frontend.hop_size)
 
 
+def critic_distance(gen, discs, mel: torch.Tensor, wav_real: torch.Tensor):
+    """The learned counterpart of :func:`copy_synthesis_error`: vocode ``mel`` [B, n_mels, T]
+    and compare the result with ``wav_real`` ([B, 1, N] or [B, N], N >= n = the vocoded
+    length) under the model's own critics.  Returns
+    ``metrics.feature_matching(discs, wav_real[..., :n], wav_fake)``, all on the device; the
+    vocoded wave rides along as its ``wav_fake`` attribute."""
+    from . import metrics
+    with torch.no_grad():
+        wav_fake = gen(mel)
+    n = wav_fake.shape[-1]
+    if not isinstance(wav_real, torch.Tensor) or wav_real.shape[-1] < n:
+        raise RuntimeError(f"critic_distance: wav_real must hold at least the {n} vocoded samples")
+    if wav_real.dim() == 2:
+        wav_real = wav_real[:, None]
+    fm = metrics.feature_matching(discs, wav_real[..., :n], wav_fake)
+    fm.wav_fake = wav_fake
+    return fm
+
+
 _RESAMPLERS = {}
 
 

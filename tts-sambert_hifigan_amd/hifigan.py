@@ -12,9 +12,15 @@ Mirrors ``models/hifigan.py`` of terrense/TTS-sambert_hifiGAN:
                            submodule tree ⇒ identical state_dict keys, same
                            ``debug_shapes`` / ``DEBUG_SHAPES`` printing, same
                            ``apply_weight_norm`` / ``remove_weight_norm``)
-* ``HiFiGAN``              models/hifigan.py:618-800, generation half
-                           (``forward`` / ``generate``); ``discriminate`` is
-                           GAN training and out of scope.
+* ``HiFiGAN``              models/hifigan.py:618-800.  By default the generation
+                           half (``forward`` / ``generate``; ``discriminate``
+                           raises, ``msd.*`` / ``mpd.*`` keys are dropped on
+                           load).  ``HiFiGAN(..., discriminators=True)`` also
+                           builds the forward-only discriminators of
+                           ``discriminators.py`` (models/hifigan.py:286-616):
+                           ``discriminate`` then returns the reference's 8-tuple.
+                           Gradients, spectral norm and any training step stay
+                           out of scope.
 
 ``HiFiGANGenerator.forward`` hands ``mel.data_ptr()``, a workspace from torch's
 caching allocator and torch's current HIP stream to ``hfg_forward_ws``; the 78
@@ -558,11 +564,14 @@ class HiFiGANGenerator(_HipWeights):
 
 
 class HiFiGAN(nn.Module):
-    """Generation half of the reference ``HiFiGAN`` wrapper (models/hifigan.py:618-800).
+    """The reference ``HiFiGAN`` wrapper (models/hifigan.py:618-800).
 
-    Accepts the reference constructor arguments; the discriminator arguments
-    are accepted and ignored because ``discriminate`` (GAN training) is out of
-    scope for this inference path.
+    Accepts the reference constructor arguments.  By default it is the generation half
+    only: ``msd`` and ``mpd`` are None, ``discriminate`` raises and ``load_state_dict`` drops
+    the ``msd.*`` / ``mpd.*`` keys.  ``discriminators=True`` (keyword only) builds the
+    forward-only critics of ``discriminators.py`` from the ``msd_*`` / ``mpd_*`` arguments,
+    keeps their keys on load (a full reference state dict then loads with ``strict=True``)
+    and makes ``discriminate`` return the reference's 8-tuple.
     """
 
     def __init__(self, n_mels: int = 80, upsample_rates: List[int] = [8, 8, 2, 2],
@@ -573,7 +582,7 @@ class HiFiGAN(nn.Module):
                  msd_use_spectral_norm: bool = False, mpd_periods: List[int] = [2, 3, 5, 7, 11],
                  mpd_use_spectral_norm: bool = False, debug_shapes: bool = False, *,
                  precision: Optional[str] = None, resblock: str = "1",
-                 final_lrelu_slope: float = 0.1):
+                 final_lrelu_slope: float = 0.1, discriminators: bool = False):
         super().__init__()
         self.debug_shapes = debug_shapes or os.getenv("DEBUG_SHAPES", "0") == "1"
         self.generator = HiFiGANGenerator(
@@ -585,6 +594,13 @@ class HiFiGAN(nn.Module):
             precision=precision, resblock=resblock, final_lrelu_slope=final_lrelu_slope)
         self.msd = None
         self.mpd = None
+        if discriminators:
+            from .discriminators import MultiPeriodDiscriminator, MultiScaleDiscriminator
+            self.msd = MultiScaleDiscriminator(use_spectral_norm=msd_use_spectral_norm,
+                                               debug_shapes=debug_shapes)
+            self.mpd = MultiPeriodDiscriminator(periods=mpd_periods,
+                                                use_spectral_norm=mpd_use_spectral_norm,
+                                                debug_shapes=debug_shapes)
 
     def forward(self, mel: torch.Tensor) -> torch.Tensor:
         """models/hifigan.py:704-724"""
@@ -600,10 +616,34 @@ class HiFiGAN(nn.Module):
         return self.forward(mel)
 
     def discriminate(self, wav_real, wav_fake):
-        raise NotImplementedError("discriminators are GAN-training only; out of scope for the "
-                                  "MI355X inference path")
+        """models/hifigan.py:726-788: the 8-tuple (msd real outputs, features, msd fake
+        outputs, features, then the same for mpd), forward only.  Real and fake run as one
+        batch of 2B: every kernel's result for an item is independent of the batch around it,
+        so each half is bitwise the separate call's.  Needs ``discriminators=True``."""
+        if self.msd is None or self.mpd is None:
+            raise NotImplementedError("this HiFiGAN was built without its discriminators "
+                                      "(forward-only critics: HiFiGAN(..., discriminators=True))")
+        if self.debug_shapes:
+            print(f"[HiFiGAN] discriminate() - Real wav shape: {wav_real.shape}")
+            print(f"[HiFiGAN] discriminate() - Fake wav shape: {wav_fake.shape}")
+        if not (isinstance(wav_real, torch.Tensor) and isinstance(wav_fake, torch.Tensor)
+                and wav_real.shape == wav_fake.shape and wav_real.dim() == 3
+                and wav_real.device == wav_fake.device):
+            raise RuntimeError("discriminate: wav_real and wav_fake must be [B, 1, T] tensors of "
+                               "one shape on one device")
+        B = wav_real.shape[0]
+        both = torch.cat([wav_real, wav_fake], dim=0)
+
+        def halves(outs, feats):
+            return ([o[:B] for o in outs], [[m[:B] for m in f] for f in feats],
+                    [o[B:] for o in outs], [[m[B:] for m in f] for f in feats])
+
+        return halves(*self.msd(both)) + halves(*self.mpd(both))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        """Accepts a full reference HiFiGAN state_dict: msd.* / mpd.* keys are dropped."""
-        sd = {k: v for k, v in state_dict.items() if not k.startswith(("msd.", "mpd."))}
-        return super().load_state_dict(sd, strict=strict, assign=assign)
+        """Accepts a full reference HiFiGAN state_dict: msd.* / mpd.* keys are dropped unless
+        the discriminators were built (``discriminators=True``)."""
+        if self.msd is None:
+            state_dict = {k: v for k, v in state_dict.items()
+                          if not k.startswith(("msd.", "mpd."))}
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)

@@ -12,7 +12,12 @@ metrics, with no gradients and no host round trip:
 * :class:`MultiResolutionSTFT` — ``compute_stft_loss`` (:625-706): mean ``|d|`` and mean
   ``d²`` of ``d = ln(|STFT a| + 1e-5) − ln(|STFT b| + 1e-5)`` over three resolutions.
 
-Both run in ``spectral_distance.hip`` (float64 FFT, float64 sums, no atomics): results are
+The remaining two terms need the model's own critics (``discriminators.py``):
+:func:`feature_matching` (``compute_feature_matching_loss``, :537-623) and
+:func:`discriminator_scores` (the pieces of ``compute_discriminator_loss`` /
+``compute_generator_adversarial_loss``, :475-535), from float64 sums formed without atomics.
+
+The spectral distances run in ``spectral_distance.hip`` (float64 FFT, float64 sums, no atomics): results are
 bitwise reproducible, item b of a ragged batch is bitwise its solo run, and the calls are
 capturable.  There is no CPU fallback: a CPU tensor raises.
 """
@@ -187,3 +192,107 @@ class MultiResolutionSTFT:
                                "must have one shape and one device")
         lens_t = _lengths(lengths, a.shape[0], a.shape[1], a.device)
         return MultiResolutionSTFTResult(d(a, b, lens_t) for d in self._dists)
+
+
+# ---------------------------------------------------------------------------------------------
+# The model's own critics (discriminators.py): the remaining VocoderLoss terms as metrics.
+
+
+class FeatureMatching:
+    """``compute_feature_matching_loss`` (models/losses.py:595-623) as numbers, all float64 on
+    the device: ``per_discriminator`` [D] (per discriminator the mean over its layers of the
+    batch mean |fake - real|), ``total`` (their mean, 0-dim) and ``per_item`` [B] (the same
+    formula restricted to item b; bitwise item b's solo value)."""
+
+    def __init__(self, per_discriminator, total, per_item):
+        self.per_discriminator, self.total, self.per_item = per_discriminator, total, per_item
+
+
+def _critic_wav(wav, what: str) -> torch.Tensor:
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
+        raise RuntimeError(f"{what} (MI355X) needs a HIP tensor; no CPU fallback")
+    if wav.dim() == 2:
+        wav = wav[:, None]
+    if wav.dim() != 3 or wav.shape[1] != 1 or wav.shape[0] < 1 or wav.shape[2] < 1:
+        raise RuntimeError(f"{what}: expected wav [B, 1, T] or [B, T], got {tuple(wav.shape)}")
+    if torch.is_grad_enabled() and wav.requires_grad:
+        raise NotImplementedError("forward-only HIP path: no autograd through the discriminators")
+    return wav.detach().to(torch.float32).contiguous()
+
+
+def feature_matching(discs, wav_real: torch.Tensor, wav_fake: torch.Tensor) -> FeatureMatching:
+    """The feature-matching distance of two waveforms under ``discs`` (an MSD, an MPD, a single
+    discriminator, a ``HiFiGAN(discriminators=True)`` or a list of those).  Real and fake run as
+    one batch of 2B through each discriminator; ``hfg_disc_fm_sums`` then adds |fake - real|
+    per (item, map) in float64 with no atomics and a fixed order.  Nothing is read back."""
+    from .discriminators import single_discriminators
+    singles = single_discriminators(discs)
+    real = _critic_wav(wav_real, "feature_matching")
+    fake = _critic_wav(wav_fake, "feature_matching")
+    if real.shape != fake.shape or real.device != fake.device:
+        raise RuntimeError(f"feature_matching: wav_real {tuple(real.shape)} and wav_fake "
+                           f"{tuple(fake.shape)} must have one shape and one device")
+    B, _, T = real.shape
+    dev = real.device
+    both = torch.cat([real, fake], dim=0)
+    per_disc, per_item = [], None
+    with torch.cuda.device(dev):
+        for d in singles:
+            d._check_input(both)
+            maps = d.run(both)
+            h = d.hip_handle(dev)
+            sums = torch.empty(B, len(maps), dtype=torch.float64, device=dev)
+            ws = torch.empty(max(h.fm_workspace_bytes(B), 16), dtype=torch.uint8, device=dev)
+            h.fm_sums(B, T, [m.data_ptr() for m in maps], [m[B:].data_ptr() for m in maps],
+                      sums.data_ptr(), ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream(dev).cuda_stream)
+            # layer means in layer order, elementwise per item: no reduction whose order could
+            # depend on the batch
+            item = None
+            for i, m in enumerate(maps):
+                term = sums[:, i] / float(m[0].numel())
+                item = term if item is None else item + term
+            item = item / float(len(maps))
+            per_disc.append(item.sum() / float(B))
+            per_item = item if per_item is None else per_item + item
+    per_disc_t = torch.stack(per_disc)
+    total = per_disc[0]
+    for v in per_disc[1:]:
+        total = total + v
+    return FeatureMatching(per_disc_t, total / float(len(singles)), per_item / float(len(singles)))
+
+
+class DiscriminatorScores:
+    """Per discriminator, over its whole score map: ``sq`` = mean d² and ``sq_minus_one`` =
+    mean (d - 1)² (float64 [D] on the device) — the pieces of the reference's LSGAN terms
+    (models/losses.py:475-535)."""
+
+    def __init__(self, sq: torch.Tensor, sq_minus_one: torch.Tensor):
+        self.sq, self.sq_minus_one = sq, sq_minus_one
+
+    @property
+    def generator_adversarial(self) -> torch.Tensor:
+        """``compute_generator_adversarial_loss`` of these (fake) scores."""
+        return self.sq_minus_one.sum() / float(self.sq_minus_one.numel())
+
+    @staticmethod
+    def discriminator_loss(real: "DiscriminatorScores", fake: "DiscriminatorScores"
+                           ) -> torch.Tensor:
+        """``compute_discriminator_loss``: the mean over discriminators of
+        mean (D(real) - 1)² + mean D(fake)²."""
+        return (real.sq_minus_one + fake.sq).sum() / float(fake.sq.numel())
+
+
+def discriminator_scores(discs, wav: torch.Tensor) -> DiscriminatorScores:
+    """The scores of ``wav`` [B, 1, T] under every single discriminator of ``discs``."""
+    from .discriminators import single_discriminators
+    singles = single_discriminators(discs)
+    x = _critic_wav(wav, "discriminator_scores")
+    sq, sq1 = [], []
+    with torch.cuda.device(x.device):
+        for d in singles:
+            d._check_input(x)
+            s = d.run(x)[-1].to(torch.float64)
+            sq.append((s * s).mean())
+            sq1.append(((s - 1.0) * (s - 1.0)).mean())
+    return DiscriminatorScores(torch.stack(sq), torch.stack(sq1))
